@@ -7,6 +7,11 @@ Multi-GPU: one process per GPU (torch.distributed / RCCL), objects sharded with 
 collective, one gather of the feature rows to rank 0 per step; weak scaling (fixed objects/GPU).
 
 Prints ONE JSON line on rank 0 (contract in the task description).
+
+A plain run sets up, warms up, times --steps steps and reports what those steps recorded; --full adds the measurements
+that take runs of their own (the CPU baseline of the numpy/scipy oracle).  --dump-outputs DIR writes what the last
+timed step computed (the feature rows and the status words) as finite DIR/<name>.npy files: float64 values with the
+non-finite entries set to 0, and DIR/<name>_nonfinite.npy (float32 codes) where those entries were.
 """
 import argparse
 import json
@@ -29,6 +34,45 @@ FP64_MFMA_PEAK_TFLOPS = 78.6   # dense fp64 matrix peak of MI355X: v_mfma_f64_16
                                # (= the fp64 vector rate; the guide's table has no fp64 row)
 NCOLS = {"stat": 123, "bazin": 52, "powerlaw": 27, "tde": 25, "color": 83, "shape": 65, "physics": 32, "gp2d": 27,
          "gp1d": 21, "research": 40}
+
+
+DUMP_BYTES = 60 << 20      # --dump-outputs writes at most this many bytes of array data (64 MB with the .npy headers)
+DUMP_SEED = 0
+
+
+def dump_rows(n_rows, row_bytes):
+    """Rows --dump-outputs writes: all of them when they fit DUMP_BYTES, else a fixed, seeded sample in ascending order
+    (the same rows whenever n_rows and row_bytes are the same)."""
+    keep = min(n_rows, DUMP_BYTES // max(row_bytes, 1))
+    if keep == n_rows:
+        return np.arange(n_rows, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, keep, replace=False)).astype(np.int64)
+
+
+def _is_float(arr):
+    return arr.is_floating_point() if hasattr(arr, "is_floating_point") else np.issubdtype(arr.dtype, np.floating)
+
+
+def dump_row_bytes(arrays):
+    """Bytes one row of ``arrays`` (name -> 2-D numpy array or tensor) takes in the files of write_outputs."""
+    return sum((12 if _is_float(v) else 8) * v.shape[1] for v in arrays.values())
+
+
+def write_outputs(path, arrays):
+    """Write each array of ``arrays`` (name -> numpy array) as float64 ``path/<name>.npy``.  Every file is finite: the
+    NaN / +inf / -inf entries of a floating-point array (features of absent bands, failed fits) are written as 0, and
+    ``path/<name>_nonfinite.npy`` (float32, same shape) holds where they were: 0 finite, 1 NaN, 2 +inf, 3 -inf."""
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        if _is_float(arr):
+            code = np.zeros(arr.shape, np.float32)
+            code[np.isnan(arr)] = 1
+            code[arr == np.inf] = 2
+            code[arr == -np.inf] = 3
+            np.save(os.path.join(path, f"{name}_nonfinite.npy"), code)
+            arr = np.where(code == 0, arr, 0.0)
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 _CPU_LC = None      # sample batch of a CPU-baseline worker
@@ -170,9 +214,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--objects", type=int, default=125000, help="objects per GPU (config 5 = 1M over 8 GPUs)")
     ap.add_argument("--sets", default="", help="comma list; default = every set the library implements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the measurements that take runs of their own (cpu_baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's feature rows and status words "
+                    "as finite float64 DIR/<name>.npy (non-finite entries 0, marked in DIR/<name>_nonfinite.npy; a fixed, seeded "
+                    "sample of rows when they exceed 64 MB)")
     ap.add_argument("--seed", type=int, default=1000000)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start one rank per GPU with torch.distributed.run as a CHILD
@@ -284,6 +334,14 @@ def main():
         dist.destroy_process_group()
         return
     per_rank = np.array([x.cpu().numpy() for x in per_rank])
+    if a.dump_outputs:
+        # what batch.run handed back in the last timed step: rank 0's feature rows and status words
+        arrays = {"features": outs[(counter[0] - 1) & 1][:n_local]}
+        if status is not None:
+            arrays["status"] = status
+        rows = torch.from_numpy(dump_rows(n_local, dump_row_bytes(arrays))).to(batch.device)
+        write_outputs(a.dump_outputs, {k: v.index_select(0, rows).cpu().numpy() for k, v in arrays.items()})
+        note(f"outputs of the last step ({rows.numel()} of {n_local} rows) written to {a.dump_outputs}")
 
     n_pts = int(lc["offsets"][-1])
     kernel_ms /= a.steps
@@ -349,7 +407,7 @@ def main():
                   "note": "step_ms = a rank's own kernel time per step (host clock around the engine call, which drains the "
                           "rank's stream); predicted_ms = dist.object_costs summed over the rank's shard"},
     }
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         note("timing the CPU oracle on the host cores")
         res["cpu_baseline"] = cpu_baseline(sets, lc)
     sys.stdout.flush()

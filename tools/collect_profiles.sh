@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 copy_csv() { find "$1" -name "*$2.csv" | head -1 | xargs -I{} cp {} "$3"; }
 # (a) serial per-kernel durations, (b) the default (concurrent) schedule
 LCFE_SERIAL=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/${R}_bench_serial.json 2> $O/serial.err && copy_csv $O/serial kernel_stats $O/${R}_bench_serial_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/default -- python3 bench.py --steps 3 --warmup 1 > $O/${R}_bench_default.json 2> $O/default.err && copy_csv $O/default kernel_stats $O/${R}_bench_default_kernel_stats.csv
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/default -- python3 bench.py --steps 3 --warmup 1 --full > $O/${R}_bench_default.json 2> $O/default.err && copy_csv $O/default kernel_stats $O/${R}_bench_default_kernel_stats.csv
 # (c) statistics set: HBM traffic and instruction counters, one counter group per pass
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --output-format csv -d $O/stat_$c -- python3 bench.py --sets stat --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> $O/stat_$c.err && copy_csv $O/stat_$c counter_collection $O/${R}_stat_pmc_$(echo $c | tr A-Z a-z).csv
