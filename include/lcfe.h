@@ -106,9 +106,11 @@ int lcfe_extract(int mask, int device, int64_t n_obj, const int64_t* offsets, co
  */
 size_t lcfe_workspace_bytes(int mask, int64_t n_obj, int64_t n_points);
 /* ... plus the slabs of the long-object tier for a batch whose longest light curve has max_len rows: light curves beyond
- * the LDS tiers (2048 rows; 1024 for the object-level fits and the research set; 767 for the 2-D GP) run with their
- * working set in global scratch, up to lcfe_max_points() rows / lcfe_gp2d_max_points() valid points.  A call whose
- * workspace holds only lcfe_workspace_bytes() leaves such objects NaN with status -100. */
+ * the LDS tiers (2048 rows; 1024 for the object-level fits and the research set; 767 for the 2-D and the per-band GP)
+ * run with their working set in global scratch, up to lcfe_max_points() rows / lcfe_gp2d_max_points() valid points
+ * (2-D GP) / lcfe_gp1d_max_points() valid points per band (per-band GP).  The per-band GP's slabs are counted only for
+ * max_len > 767, so batches of shorter light curves keep the size of lcfe_workspace_bytes().  A call whose workspace
+ * holds only lcfe_workspace_bytes() leaves such objects NaN with status -100. */
 size_t lcfe_workspace_bytes_for(int mask, int64_t n_obj, int64_t n_points, int64_t max_len);
 int lcfe_extract_device(int mask, int device, void* stream, int64_t n_obj, int64_t n_points,
                         int64_t max_len, const int64_t* d_offsets, const double* d_t,
@@ -124,6 +126,9 @@ void lcfe_release_buffers(void);
 int64_t lcfe_max_points(void);
 /* largest number of VALID points (known band, finite flux and error, error > 0) per object the 2-D GP accepts */
 int64_t lcfe_gp2d_max_points(void);
+/* largest number of VALID points in one band (g, r, i or z) the per-band GP fits; a band with more gets NaN in its four
+ * columns and status -100 in its status word, the other bands of the object are still fitted */
+int64_t lcfe_gp1d_max_points(void);
 /* mask of the feature sets this build of the library implements */
 int lcfe_implemented_mask(void);
 

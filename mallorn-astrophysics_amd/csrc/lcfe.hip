@@ -1302,11 +1302,148 @@ int launch_gp1d_tier(const BatchView& B, const Bins& bins, int bin, int nan_from
     return 0;
 }
 
+// ---- the long-object tier of the per-band GP: light curves of more than 767 rows (GP bin 6), up to kLongCap rows, each band
+// up to kGp1dLongTierNP - 1 valid points -- the 2-D GP's limits.  One light curve per workgroup of kGp1dThreads threads, its
+// bands one after the other on the whole workgroup, persistent over bin 6 through one ticket counter.  The Gram matrix
+// (gp_store_doubles(2048) doubles, 16.9 MB) AND the working set (Gp1dLds<2048, 4> in global scratch, 366 KB) sit in a
+// per-workgroup slab; LDS holds the row lists only: 32 KiB of valid row indices partitioned by band + 4 KiB for the rank
+// sort of one band + < 1 KiB of counters = 37 KiB of the 160 KiB.
+// Grid: 8 workgroups (the 2-D GP's long tier has 8 too): 8 slabs are 138 MB of workspace, 16 would be 276 MB for a tier
+// that sees a handful of light curves per batch.  Tickets are served in file order: ordering them longest first would need
+// another n_obj-entry index list in every workspace (the one bin-6 list is read by the 2-D GP's long kernel at the same time).
+constexpr int kGp1dLongTierNP = kGpLongNP;
+constexpr int kGp1dLongTierGrid = 8;
+using Gp1dLongTierWs = Gp1dLds<kGp1dLongTierNP, kGp1dThreads / 64, false>;
+constexpr size_t kGp1dLongTierSBytes = (sizeof(Gp1dLongTierWs) + 255) & ~(size_t)255;
+constexpr size_t kGp1dLongTierBytes = (size_t)kGp1dLongTierGrid * ((size_t)gp_store_doubles(kGp1dLongTierNP) * 8 + kGp1dLongTierSBytes);
+
+// slabs: kGp1dLongTierGrid Gram matrices, then kGp1dLongTierGrid working sets.  Light curves of more than kLongCap rows keep
+// the NaN row and status -100 the tier-5 launch wrote.
+__global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B, Bins bins, double* out, int ld, int col0, int32_t* status,
+                                                                   int st_ld, int st0, char* slabs, unsigned long long* ticket) {
+    constexpr int T = kGp1dThreads, NP = kGp1dLongTierNP;
+    using W = BlockDev<T>;
+    __shared__ unsigned short rows[kLongCap];          // valid rows of g, r, i, z, partitioned by band, each part in time order
+    __shared__ unsigned short rows2[NP];               // rank sort of one band (bands of at most NP - 1 valid points only)
+    __shared__ double orow[GP1D_NCOL + 3];
+    __shared__ int boff[5], nall[4];
+    __shared__ int wcnt[T / 64][4];
+    __shared__ long long next_ticket;
+    double* Kg = reinterpret_cast<double*>(slabs) + (size_t)blockIdx.x * (size_t)gp_store_doubles(NP);
+    Gp1dLongTierWs& S = *reinterpret_cast<Gp1dLongTierWs*>(slabs + (size_t)kGp1dLongTierGrid * gp_store_doubles(NP) * 8 +
+                                                         (size_t)blockIdx.x * kGp1dLongTierSBytes);
+    const int count = bins.counts[kNumBins + 6];
+    const int* list = bins.lists + (int64_t)(kNumBins + 6) * bins.stride;
+    for (;;) {
+        if (threadIdx.x == 0) next_ticket = (long long)atomicAdd(ticket, 1ull);
+        __syncthreads();
+        const int64_t pos = next_ticket;
+        __syncthreads();
+        if (pos >= count) break;
+        // (uniform by construction; said explicitly, so that the branches on the length and the loops over the rows are
+        //  scalar -- DESIGN §3: a per-lane length once turned the ticket loop into an endless re-read of one ticket)
+        const int64_t i = __builtin_amdgcn_readfirstlane(list[pos]);
+        const int64_t s = B.offsets[i];
+        const int64_t n64 = B.offsets[i + 1] - s;
+        const int n = __builtin_amdgcn_readfirstlane((int)((n64 > kLongCap) ? kLongCap + 1 : n64));
+        if (n <= kLongCap) {
+            const double* t = B.t + s;
+            const double* f = B.f + s;
+            const double* e = B.e + s;
+            const uint8_t* bb = B.b + s;
+            int32_t* st = status ? status + i * (int64_t)st_ld + st0 : nullptr;
+            auto valid = [&](int k) { return !is_nan(f[k]) && !is_nan(e[k]) && e[k] > 0; };
+            // ---- rows per band (the cross-band columns take a band with >= 5 rows) and VALID rows per band
+            int cnt[4] = {0, 0, 0, 0}, nv[4] = {0, 0, 0, 0};
+            for (int k = threadIdx.x; k < n; k += T) {
+                const int band = bb[k];
+                if (band < 1 || band > 4) continue;
+                ++cnt[band - 1];
+                if (valid(k)) ++nv[band - 1];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { cnt[j] = W::sum(cnt[j]); nv[j] = W::sum(nv[j]); }
+            if (threadIdx.x == 0) {
+                boff[0] = 0;
+                for (int j = 0; j < 4; ++j) { boff[j + 1] = boff[j] + nv[j]; nall[j] = cnt[j]; }
+            }
+            __syncthreads();
+            // stable partition of the valid rows by band (gp1d_kernel's ballot ranks): one pass, O(n) per object
+            {
+                int run[4] = {0, 0, 0, 0};
+                for (int base = 0; base < n; base += T) {
+                    const int k = base + (int)threadIdx.x;
+                    const int band = (k < n && valid(k)) ? (int)bb[k] : 0;
+                    int rank = 0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const unsigned long long mk = __ballot(band == j + 1);
+                        if (band == j + 1) rank = WaveDev::prefix(mk);
+                        if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6][j] = popcll(mk);
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        int before = 0, total = 0;
+                        for (int wv = 0; wv < T / 64; ++wv) { const int c = wcnt[wv][j]; total += c; before += (wv < (int)(threadIdx.x >> 6)) ? c : 0; }
+                        if (band == j + 1) rows[boff[j] + run[j] + before + rank] = (unsigned short)k;
+                        run[j] += total;
+                    }
+                    __syncthreads();
+                }
+            }
+            bool ordered = true;
+            for (int k = threadIdx.x; k + 1 < n; k += T) ordered = ordered && (t[k] <= t[k + 1]);
+            if (!W::all(ordered)) {
+                // stable rank sort of every band part by (time, file index), as the oracle's ``band_sorted`` (a NaN time
+                // last, so that the ranks are a permutation whatever the input).  Only bands the fit takes: at most
+                // NP - 1 = 2047 valid points, i.e. at most 2047^2 / 256 = 16 k comparisons per thread and band.
+                for (int j = 0; j < 4; ++j) {
+                    const int b0 = boff[j], m = boff[j + 1] - b0;
+                    if (m + 1 > NP) continue;
+                    for (int k = threadIdx.x; k < m; k += T) {
+                        const double tk = t[rows[b0 + k]];
+                        const bool nk = is_nan(tk);
+                        int r = 0;
+                        for (int q = 0; q < m; ++q) {
+                            const double tq = t[rows[b0 + q]];
+                            const bool nq = is_nan(tq);
+                            const bool lt = (nq == nk) ? (nk ? q < k : (tq < tk || (tq == tk && q < k))) : nk;
+                            r += lt ? 1 : 0;
+                        }
+                        rows2[r] = rows[b0 + k];
+                    }
+                    __syncthreads();
+                    for (int k = threadIdx.x; k < m; k += T) rows[b0 + k] = rows2[k];
+                    __syncthreads();
+                }
+            }
+            bool fitted[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) fitted[j] = nall[j] >= 5;
+            for (int j = 0; j < 4; ++j) {
+                const int b0 = boff[j], m = boff[j + 1] - b0;
+                gp1d_band<W, NP, true>([&](int r, double& tt, double& ff, double& ee) { const int k = rows[b0 + r]; tt = t[k]; ff = f[k]; ee = e[k]; },
+                                       m, S,
+                                       [&](const double* x, int nn, double& fv, double* gv) { gp1d_eval<W, NP, global_double*>(x, nn, S, (global_double*)Kg, fv, gv); },
+                                       orow + 4 * j, st ? st + j : nullptr);
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) gp1d_cross_band(orow, fitted);
+            __syncthreads();
+            store_row<W>(orow, out + i * (int64_t)ld + col0, GP1D_NCOL);
+        }
+        __syncthreads();
+    }
+}
+
 // The GP bins are reused (by rows of the whole object): bins 0..2 run with a Gram matrix as large as the
-// object; bins 3..5 (160..767 rows) with the 160-row matrix -- a band with more than 159 valid points
-// gets NaN and status -100.
+// object; bins 3..5 (160..767 rows) with the 160-row matrix, a band of 160..767 valid points with the 768-row one in
+// global scratch; bin 6 (more than 767 rows) in the long-object tier when the workspace holds its slabs (long_slab),
+// NaN and status -100 otherwise.
 int launch_gp1d(const BatchView& B, const Bins& bins, int64_t max_len, double* out, int ld, int col0, int32_t* status,
-                int st_ld, int st0, hipStream_t stream, int dev, int* n_launch, unsigned long long* tickets, double* kslab) {
+                int st_ld, int st0, hipStream_t stream, int dev, int* n_launch, unsigned long long* tickets, double* kslab,
+                char* long_slab) {
     const int caps[6] = {63, 111, 159, kGpSmallNP - 1, kGpMidNP - 1, kGpGlobalNP - 1};
     int last = 0;
     while (last < 5 && caps[last] < max_len) ++last;
@@ -1321,6 +1458,15 @@ int launch_gp1d(const BatchView& B, const Bins& bins, int64_t max_len, double* o
             default: rc = launch_gp1d_tier<160, 768, kGp1dThreads, 64, 1>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk, kslab); break;
         }
         if (rc) return rc;
+        ++*n_launch;
+    }
+    // light curves of more than 767 rows (bin 6): they overwrite the NaN rows and status -100 of the tier-5 launch, which
+    // ran before them on this stream.  Last on the stream, so that the short tiers do not wait for 8 workgroups that may
+    // take seconds per light curve.
+    if (long_slab && max_len > kGpGlobalNP - 1) {
+        hipLaunchKernelGGL(gp1d_long_kernel, dim3(kGp1dLongTierGrid), dim3(kGp1dThreads), 0, stream, B, bins, out, ld, col0, status,
+                           st_ld, st0, long_slab, tickets + SET_GP1D * 8 + 7);
+        HIP_TRY(hipGetLastError());
         ++*n_launch;
     }
     return 0;
@@ -1799,6 +1945,8 @@ int64_t lcfe_max_points(void) { return kLongCap; }
 
 int64_t lcfe_gp2d_max_points(void) { return kGpLongNP - 1; }
 
+int64_t lcfe_gp1d_max_points(void) { return kGp1dLongTierNP - 1; }
+
 int lcfe_implemented_mask(void) {
     int m = 0;
     for (int s = 0; s < NUM_SETS; ++s)
@@ -1856,6 +2004,7 @@ static size_t long_bytes_of(int set, int64_t max_len) {
         case SET_SHAPE: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_SHAPE>() : 0;
         case SET_PHYSICS: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_PHYSICS>() : 0;
         case SET_GP2D: return (max_len > kGpGlobalNP - 1) ? kGpLongBytes : 0;
+        case SET_GP1D: return (max_len > kGpGlobalNP - 1) ? kGp1dLongTierBytes : 0;
         case SET_RESEARCH: return kLongGrid * long_slab_bytes<SET_RESEARCH>();     // (an r band of more than 4096 days can sit in a short light curve)
     }
     return 0;
@@ -2002,7 +2151,7 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
             case SET_SHAPE: rc = launch_set<SET_SHAPE>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
             case SET_PHYSICS: rc = launch_set<SET_PHYSICS>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
             case SET_RESEARCH: rc = launch_set<SET_RESEARCH>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
-            case SET_GP1D: rc = launch_gp1d(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, gp1d_slab); break;
+            case SET_GP1D: rc = launch_gp1d(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, gp1d_slab, long_slab[s]); break;
             case SET_GP2D:
             {
                 // the GP tiers, longest first, round-robin over the caller's stream and side streams 2.. (LCFE_GP_STREAMS, default

@@ -27,8 +27,8 @@ NEEDS_Z = {"physics", "research"}
 def _limit_message(set_name, csr, rows, lib):
     """What the objects `rows` of a set ran into (status -100): the message names the limit that was hit, so that a
     limit-NaN can be told from a failed fit.  The LDS tiers end at 2048 rows (1024 for the object-level fits and the
-    research set, 767 for the 2-D GP); longer light curves run in the long-object tier (working set in global scratch),
-    whose limits are the ones reported here."""
+    research set, 767 for the 2-D and the per-band GP); longer light curves run in the long-object tier (working set in
+    global scratch), whose limits are the ones reported here."""
     n = np.diff(csr["offsets"])[rows]
     max_rows = int(lib.lcfe_max_points())
     over_rows = int((n > max_rows).sum())
@@ -38,7 +38,7 @@ def _limit_message(set_name, csr, rows, lib):
         if set_name == "gp2d":
             parts.append(f"{rest} with more than {int(lib.lcfe_gp2d_max_points())} valid points")
         elif set_name == "gp1d":
-            parts.append(f"{rest} with a band of more than 767 valid points or more than 767 rows")
+            parts.append(f"{rest} with a band of more than {int(lib.lcfe_gp1d_max_points())} valid points")
         elif set_name == "research":
             parts.append(f"{rest} whose r band spans more than 65536 days (the Mexican-hat grid of the long-object tier)")
         else:
