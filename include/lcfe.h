@@ -45,7 +45,9 @@ enum {
     LCFE_SET_GP1D = 8,     /* gaussian_process.py:173-310    21 columns (per-band scikit-learn GP) */
     LCFE_SET_RESEARCH = 9, /* research_features.py:533-600   40 columns (v115: log-log power law, nuclear proxy,
                               colour at peak, Mexican-hat power spectra, luminosity; reads z) */
-    LCFE_NUM_SETS = 10
+    LCFE_SET_ECOLOR = 10,  /* enhanced_colors.py:81-189     45 columns (opt-in: colours at 0..150 days after the g peak) */
+    LCFE_SET_DECLINE = 11, /* time_to_decline.py:110-175    36 columns (opt-in: time from the peak to 80..10 % per band) */
+    LCFE_NUM_SETS = 12
 };
 #define LCFE_MASK(id) (1 << (id))
 #define LCFE_MASK_ALL ((1 << LCFE_NUM_SETS) - 1)
@@ -65,6 +67,7 @@ typedef struct lcfe_stats {
     int32_t reserved;
 } lcfe_stats;
 
+/* 2 since LCFE_NUM_SETS = 12 (lcfe_stats grew): C callers must recompile against this header */
 int lcfe_version(void);
 /* number of visible HIP devices (0 if none) */
 int lcfe_device_count(void);

@@ -10,8 +10,12 @@ The integer ids / bit masks below are the same constants as ``include/lcfe.h``.
 BANDS = ["u", "g", "r", "i", "z", "y"]
 
 # feature-set ids (bit = 1 << id) -- keep in sync with include/lcfe.h
-SET_STAT, SET_BAZIN, SET_POWERLAW, SET_TDE, SET_COLOR, SET_SHAPE, SET_PHYSICS, SET_GP2D, SET_GP1D, SET_RESEARCH = range(10)
-SET_NAMES = ["stat", "bazin", "powerlaw", "tde", "color", "shape", "physics", "gp2d", "gp1d", "research"]
+(SET_STAT, SET_BAZIN, SET_POWERLAW, SET_TDE, SET_COLOR, SET_SHAPE, SET_PHYSICS, SET_GP2D, SET_GP1D, SET_RESEARCH,
+ SET_ECOLOR, SET_DECLINE) = range(12)
+SET_NAMES = ["stat", "bazin", "powerlaw", "tde", "color", "shape", "physics", "gp2d", "gp1d", "research",
+             "ecolor", "decline"]
+# what ``extract_all(sets=None)`` runs: the ten sets before the opt-in post-peak sets (ecolor, decline)
+DEFAULT_SETS = SET_NAMES[:10]
 
 _STAT17 = ["n_obs", "mean", "std", "min", "max", "median", "skew", "kurtosis", "amplitude", "mad",
            "iqr", "beyond_1std", "beyond_2std", "max_slope", "mean_snr", "time_span", "cadence_mean"]
@@ -143,12 +147,33 @@ def _research():
     return cols
 
 
+ECOLOR_PAIRS = ["ug", "gr", "ri", "iz"]
+ECOLOR_EPOCHS = [0, 10, 20, 30, 50, 75, 100, 150]
+
+
+def _ecolor():
+    # enhanced_colors.py:132-187 (epoch-major, pair-minor; then per pair dispersion / range / mean)
+    cols = [f"{p}_color_{e}d" for e in ECOLOR_EPOCHS for p in ECOLOR_PAIRS]
+    for p in ECOLOR_PAIRS:
+        cols += [f"{p}_color_dispersion", f"{p}_color_range", f"{p}_color_mean"]
+    return cols + ["gr_ri_color_correlation"]
+
+
+def _decline():
+    # time_to_decline.py:128-173
+    cols = []
+    for b in BANDS:
+        cols += [f"{b}_decline_to_{p}pct" for p in (80, 60, 40, 20, 10)] + [f"{b}_decline_velocity"]
+    return cols
+
+
 COLUMNS = {"stat": _stat(), "bazin": _bazin(), "powerlaw": _powerlaw(), "tde": _tde(),
            "color": _color(), "shape": _shape(), "physics": _physics(), "gp2d": _gp2d(), "gp1d": _gp1d(),
-           "research": _research()}
+           "research": _research(), "ecolor": _ecolor(), "decline": _decline()}
 NCOLS = {k: len(v) for k, v in COLUMNS.items()}
 assert NCOLS == {"stat": 123, "bazin": 52, "powerlaw": 27, "tde": 25, "color": 83, "shape": 65,
-                 "physics": 32, "gp2d": 27, "gp1d": 21, "research": 40}, NCOLS
+                 "physics": 32, "gp2d": 27, "gp1d": 21, "research": 40, "ecolor": 45,
+                 "decline": 36}, NCOLS
 
 # integer-valued columns of the statistics frame (int64 in the reference's DataFrame)
 STAT_INT_COLUMNS = [f"{p}_n_obs" for p in BANDS + ["all"]] + ["peak_band"]

@@ -10,10 +10,13 @@
 #include "physics.hpp"
 #include "gp.hpp"
 #include "research.hpp"
+#include "ecolor.hpp"
+#include "decline.hpp"
 
 namespace lcfe {
 
-enum { SET_STAT = 0, SET_BAZIN, SET_POWERLAW, SET_TDE, SET_COLOR, SET_SHAPE, SET_PHYSICS, SET_GP2D, SET_GP1D, SET_RESEARCH, NUM_SETS };
+enum { SET_STAT = 0, SET_BAZIN, SET_POWERLAW, SET_TDE, SET_COLOR, SET_SHAPE, SET_PHYSICS, SET_GP2D, SET_GP1D, SET_RESEARCH, SET_ECOLOR,
+       SET_DECLINE, NUM_SETS };
 
 LCFE_HD int set_ncols(int set) {
     switch (set) {
@@ -27,6 +30,8 @@ LCFE_HD int set_ncols(int set) {
         case SET_GP2D: return 27;
         case SET_GP1D: return 21;
         case SET_RESEARCH: return 40;
+        case SET_ECOLOR: return 45;
+        case SET_DECLINE: return 36;
     }
     return 0;
 }
@@ -92,6 +97,17 @@ template <int CAP>
 struct SetLds<SET_RESEARCH, CAP> {
     ObjLds<CAP> obj;
     ResearchLds<CAP> s;
+};
+
+template <int CAP>
+struct SetLds<SET_ECOLOR, CAP> {
+    ObjLds<CAP> obj;
+    EcolorLds s;
+};
+template <int CAP>
+struct SetLds<SET_DECLINE, CAP> {
+    ObjLds<CAP> obj;
+    DeclineLds s;
 };
 
 // copy `ncol` wave-shared doubles to the object's output row (coalesced on the device)
@@ -203,6 +219,27 @@ struct RunSet<W, SET_RESEARCH, CAP> {
         store_row<W>(ws.s.out, row, RESEARCH_NCOL);
         W::sync();
         return rc;
+    }
+};
+
+template <class W, int CAP>
+struct RunSet<W, SET_ECOLOR, CAP> {
+    static LCFE_FN int run(const ObjIn& in, SetLds<SET_ECOLOR, CAP>& ws, double* row, int32_t*) {
+        stage_object<W, CAP>(in, ws.obj);
+        ecolor_object<W, CAP>(ws.obj, ws.s);
+        store_row<W>(ws.s.out, row, ECOLOR_NCOL);
+        W::sync();
+        return 0;
+    }
+};
+template <class W, int CAP>
+struct RunSet<W, SET_DECLINE, CAP> {
+    static LCFE_FN int run(const ObjIn& in, SetLds<SET_DECLINE, CAP>& ws, double* row, int32_t*) {
+        stage_object<W, CAP>(in, ws.obj);
+        decline_object<W, CAP>(ws.obj, ws.s);
+        store_row<W>(ws.s.out, row, DECLINE_NCOL);
+        W::sync();
+        return 0;
     }
 };
 

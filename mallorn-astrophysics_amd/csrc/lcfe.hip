@@ -1931,7 +1931,7 @@ int lcfe_debug_phase_prof(unsigned long long* out32) {
 }
 #endif
 
-int lcfe_version(void) { return 1; }
+int lcfe_version(void) { return 2; }     // 2: lcfe_stats grew with LCFE_NUM_SETS = 12
 
 int lcfe_device_count(void) {
     int n = 0;
@@ -1978,9 +1978,10 @@ const char* lcfe_colname(int mask, int64_t j) {
     return nullptr;
 }
 
-// workspace layout: [0, 1024) ticket counters (8 per set), [1024, 2048) bin counts, then the
+// workspace layout: [0, 1024) ticket counters (8 per set, room for 16 sets), [1024, 2048) bin counts, then the
 // kNumLists index lists of n_obj int32 each (256-byte aligned total), then the GP scratch slabs
 constexpr size_t kWsHeader = 2048;
+static_assert(NUM_SETS * 8 * sizeof(unsigned long long) <= 1024, "ticket counters of every set fit the header");
 static size_t list_bytes(int64_t n_obj) {
     return (((size_t)(n_obj > 0 ? n_obj : 0) * kNumLists * sizeof(int)) + 255) & ~(size_t)255;
 }
@@ -2006,6 +2007,8 @@ static size_t long_bytes_of(int set, int64_t max_len) {
         case SET_GP2D: return (max_len > kGpGlobalNP - 1) ? kGpLongBytes : 0;
         case SET_GP1D: return (max_len > kGpGlobalNP - 1) ? kGp1dLongTierBytes : 0;
         case SET_RESEARCH: return kLongGrid * long_slab_bytes<SET_RESEARCH>();     // (an r band of more than 4096 days can sit in a short light curve)
+        case SET_ECOLOR: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_ECOLOR>() : 0;
+        case SET_DECLINE: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_DECLINE>() : 0;
     }
     return 0;
 }
@@ -2094,7 +2097,8 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
         switch (s) {
             case SET_BAZIN: return side[0];
             case SET_POWERLAW: return side[1];
-            case SET_TDE: case SET_COLOR: case SET_SHAPE: case SET_PHYSICS: case SET_GP1D: case SET_RESEARCH: return side[2];
+            case SET_TDE: case SET_COLOR: case SET_SHAPE: case SET_PHYSICS: case SET_GP1D: case SET_RESEARCH:
+            case SET_ECOLOR: case SET_DECLINE: return side[2];
             default: return stream;
         }
     };
@@ -2151,6 +2155,8 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
             case SET_SHAPE: rc = launch_set<SET_SHAPE>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
             case SET_PHYSICS: rc = launch_set<SET_PHYSICS>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
             case SET_RESEARCH: rc = launch_set<SET_RESEARCH>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
+            case SET_ECOLOR: rc = launch_set<SET_ECOLOR>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
+            case SET_DECLINE: rc = launch_set<SET_DECLINE>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
             case SET_GP1D: rc = launch_gp1d(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, gp1d_slab, long_slab[s]); break;
             case SET_GP2D:
             {

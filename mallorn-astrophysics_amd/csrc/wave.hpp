@@ -345,6 +345,16 @@ __device__ __forceinline__ unsigned long long* phase_prof_lds() {
 
 LCFE_FN int popcll(unsigned long long m) { return __builtin_popcountll(m); }
 
+// A value every lane of the wavefront holds (read from LDS, or a reduction result), made uniform for the compiler before
+// it steers control flow.  All lanes must be active.  Identity on the host.
+LCFE_FN int uniform_int(int v) {
+#if defined(__HIPCC__)
+    return __builtin_amdgcn_readfirstlane(v);
+#else
+    return v;
+#endif
+}
+
 // quiet NaN without relying on host/device library differences
 LCFE_FN double qnan() { return __builtin_nan(""); }
 LCFE_FN bool is_nan(double x) { return x != x; }

@@ -11,7 +11,7 @@ import warnings
 
 import numpy as np
 
-from ..columns import COLUMNS, SET_NAMES, STAT_INT_COLUMNS
+from ..columns import COLUMNS, DEFAULT_SETS, STAT_INT_COLUMNS, SET_NAMES
 from ..engine import extract_csr, mask_of, sets_of
 from ..packing import pack_lightcurves
 
@@ -22,6 +22,9 @@ ID_FIRST = {"stat", "powerlaw"}
 INT_COLUMNS = {"stat": STAT_INT_COLUMNS}
 # sets that read the redshift column of the metadata (physics_based.py:481, research_features.py:552-559)
 NEEDS_Z = {"physics", "research"}
+# sets whose reference batch function returns one row per REQUESTED id -- an id without rows gets the all-NaN row -- and
+# then fills every NaN with its column's median (enhanced_colors.py:236-260, time_to_decline.py:213-233)
+FILLED = {"ecolor", "decline"}
 
 
 def _limit_message(set_name, csr, rows, lib):
@@ -78,6 +81,32 @@ def frame_of(set_name, block, kept):
     return df
 
 
+def filled_frame(set_name, block, kept, requested):
+    """The frame of a FILLED set: one row per id of ``requested`` in request order (``kept`` is the subsequence of it
+    that has rows, repeats included; the others get the NaN row), then the reference's per-column median fill -- NaN
+    becomes the column's median, or 0.0 when the whole column is NaN -- and ``object_id`` last."""
+    import pandas as pd
+
+    cols = COLUMNS[set_name]
+    block = np.asarray(block, np.float64)
+    rows = np.full((len(requested), len(cols)), np.nan)
+    j = 0
+    for r, i in enumerate(requested):
+        if j < len(kept) and kept[j] == i:
+            rows[r] = block[j]
+            j += 1
+    if j != len(kept):
+        raise ValueError("kept ids are not a subsequence of the requested ids")
+    df = pd.DataFrame(rows, columns=cols)
+    df["object_id"] = list(requested)
+    for col in cols:                                              # enhanced_colors.py:255-260, time_to_decline.py:228-233
+        median_val = df[col].median()
+        if np.isnan(median_val):
+            median_val = 0.0
+        df[col] = df[col].fillna(median_val)
+    return df
+
+
 def redshifts(metadata, kept):
     """z per kept object: ``z_lookup.get(obj_id, nan)`` (physics_based.py:481,496)."""
     zmap = dict(zip(metadata["object_id"], metadata["Z"]))
@@ -96,13 +125,15 @@ def extract_all(lightcurves=None, metadata=None, object_ids=None, sets=None, csr
 
     ``lightcurves``: the long frame (``object_id, Time (MJD), Flux, Flux_err, Filter``), or pass ``csr=(csr, ids)``
     as ``utils.data_loader.load_lightcurves_csr`` / ``packing.pack_lightcurves`` return it (``object_ids`` then selects
-    and orders objects of that batch).  ``sets``: names (default: all ten).  Returns ``{set name: DataFrame}`` with the
-    reference's conventions per extractor; with ``return_matrix`` also the raw ``(matrix, status, kept_ids)``."""
+    and orders objects of that batch).  ``sets``: names (default: the ten sets before the opt-in post-peak sets ``ecolor``
+    and ``decline``, which run only when named).  Returns ``{set name: DataFrame}`` with the reference's conventions per
+    extractor -- the post-peak frames have one row per requested id and are median-filled as the reference's are; with
+    ``return_matrix`` also the raw, unfilled ``(matrix, status, kept_ids)``."""
     from .. import _lib
     from ..packing import select_objects
 
     lib = _lib.load()
-    names = sets_of(mask_of(list(SET_NAMES) if sets is None else sets))         # canonical (column) order
+    names = sets_of(mask_of(list(DEFAULT_SETS) if sets is None else sets))         # canonical (column) order
     mask = mask_of(names)
     if csr is not None:
         batch, ids = csr
@@ -123,7 +154,11 @@ def extract_all(lightcurves=None, metadata=None, object_ids=None, sets=None, csr
     frames, col0 = {}, 0
     for name in names:
         ncol = len(COLUMNS[name])
-        frames[name] = frame_of(name, out[:, col0:col0 + ncol], kept)
+        if name in FILLED:
+            requested = kept if object_ids is None else list(object_ids)
+            frames[name] = filled_frame(name, out[:, col0:col0 + ncol], kept, requested)
+        else:
+            frames[name] = frame_of(name, out[:, col0:col0 + ncol], kept)
         col0 += ncol
     if return_matrix:
         return frames, (out, status, kept)
