@@ -52,6 +52,19 @@ enum {
 #define LCFE_MASK(id) (1 << (id))
 #define LCFE_MASK_ALL ((1 << LCFE_NUM_SETS) - 1)
 
+/* Extension sets.  They are selected like the numbered sets, by LCFE_MASK(id) in the mask of any entry point, and their
+ * columns and status words follow those of the numbered sets in increasing id order.  But they are NOT counted by
+ * LCFE_NUM_SETS, have no slot in lcfe_stats, and are not part of LCFE_MASK_ALL or lcfe_implemented_mask(): adding one
+ * changes neither sizeof(lcfe_stats) nor lcfe_version(), so callers compiled against an older header keep working
+ * without a recompile.  Which ones a library has: lcfe_implemented_xmask().  Their kernel times: lcfe_last_ext_profile().
+ * One call runs numbered and extension sets together on the same side streams; a mask of extension bits only is valid. */
+enum {
+    LCFE_XSET_ADVANCED = 12, /* advanced_features.py:476-622   50 columns (opt-in: absolute magnitudes, Mexican-hat power
+                                spectra of r and g over all pairs of a band, FLEET widths, pre-peak colours, autocorrelation,
+                                early / late ratios, higher-order statistics, peak lags; reads z) */
+    LCFE_NUM_XSETS = 1
+};
+
 /* Per-call profile, filled when a non-NULL pointer is passed.  kernel_ms[s] is the HIP-event time
  * of feature set s's kernel(s) on the stream they were launched on.  The statistics set (with the
  * shared binning prologue) runs alone; the other sets run concurrently on internal side streams
@@ -61,7 +74,8 @@ typedef struct lcfe_stats {
     double kernel_ms[LCFE_NUM_SETS];
     double h2d_ms;          /* host-buffer entry point only */
     double d2h_ms;
-    int64_t bytes_in;       /* algorithmic input bytes: 25 * n_points + 8 * (n_obj + 1) [+ 8 * n_obj for z] */
+    int64_t bytes_in;       /* algorithmic input bytes: 25 * n_points + 8 * (n_obj + 1) [+ 8 * n_obj when a z array is
+                               passed: read by LCFE_SET_PHYSICS, LCFE_SET_RESEARCH and LCFE_XSET_ADVANCED] */
     int64_t bytes_out;      /* 8 * n_obj * ncols */
     int32_t launches[LCFE_NUM_SETS];
     int32_t reserved;
@@ -80,7 +94,8 @@ int64_t lcfe_ncols(int mask);
 const char* lcfe_colname(int mask, int64_t j);
 /* int32 status words per object for a mask: Bazin 6 x (status, nfev), power-law 27 x (status, nfev),
  * GP 4 (status, n_iter, n_eval, n_points), per-band GP 4 (L-BFGS-B evaluations of g, r, i, z; -100: band
- * longer than 159 valid points); 0 for the other sets */
+ * longer than 159 valid points), research 1 and LCFE_XSET_ADVANCED 1 (0, or -100: the r band spans more days than the
+ * set's 1-day grid takes -- 65536 / 4194304 -- and the columns computed on that grid are NaN); 0 for the other sets */
 int64_t lcfe_nstatus(int mask);
 
 /*
@@ -88,8 +103,8 @@ int64_t lcfe_nstatus(int mask);
  * (-1 = current device), runs the kernels of every set in `mask`, copies results back.
  *   offsets  int64[n_obj+1], offsets[0] == 0, non-decreasing
  *   t, flux, err  float64[offsets[n_obj]]   band  uint8[offsets[n_obj]]
- *   z        float64[n_obj] redshift (used by LCFE_SET_PHYSICS and LCFE_SET_RESEARCH; NULL or NaN entries = 0,
- *            physics_based.py:348)
+ *   z        float64[n_obj] redshift (used by LCFE_SET_PHYSICS, LCFE_SET_RESEARCH and LCFE_XSET_ADVANCED; NULL or NaN
+ *            entries = 0, physics_based.py:348; the advanced set's absolute magnitudes are NaN unless z > 0)
  *   out      float64[n_obj * lcfe_ncols(mask)] row-major
  *   status   int32[n_obj * lcfe_nstatus(mask)] or NULL
  */
@@ -132,8 +147,14 @@ int64_t lcfe_gp2d_max_points(void);
 /* largest number of VALID points in one band (g, r, i or z) the per-band GP fits; a band with more gets NaN in its four
  * columns and status -100 in its status word, the other bands of the object are still fitted */
 int64_t lcfe_gp1d_max_points(void);
-/* mask of the feature sets this build of the library implements */
+/* mask of the numbered feature sets (ids below LCFE_NUM_SETS) this build of the library implements */
 int lcfe_implemented_mask(void);
+/* mask of the extension sets (LCFE_XSET_*) this build implements; the two masks share no bit */
+int lcfe_implemented_xmask(void);
+/* kernel time (HIP events, ms) and launch count of the extension sets of the last lcfe_extract / lcfe_extract_device call
+ * this THREAD made with prof != NULL: entry k belongs to extension set LCFE_NUM_SETS + k; sets that were not in that
+ * call's mask read 0.  Fills min(n, LCFE_NUM_XSETS) entries of each non-NULL array and returns LCFE_NUM_XSETS. */
+int lcfe_last_ext_profile(double* kernel_ms, int32_t* launches, int n);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LCFE_LIB_PATH") or os.path.join(_HERE, "csrc", "liblcfe.so")   # override: instrumented builds
-NUM_SETS = 12
+NUM_SETS = 12           # numbered sets (lcfe_stats); the extension sets are columns.EXT_SET_NAMES
 
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_f64p = ctypes.POINTER(ctypes.c_double)
@@ -84,6 +84,9 @@ def load():
     lib.lcfe_gp2d_max_points.restype = ctypes.c_int64
     lib.lcfe_gp1d_max_points.restype = ctypes.c_int64
     lib.lcfe_implemented_mask.restype = ctypes.c_int
+    lib.lcfe_implemented_xmask.restype = ctypes.c_int
+    lib.lcfe_last_ext_profile.restype = ctypes.c_int
+    lib.lcfe_last_ext_profile.argtypes = [c_f64p, c_i32p, ctypes.c_int]
     lib.lcfe_workspace_bytes.restype = ctypes.c_size_t
     lib.lcfe_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int64]
     lib.lcfe_workspace_bytes_for.restype = ctypes.c_size_t

@@ -16,6 +16,11 @@ SET_NAMES = ["stat", "bazin", "powerlaw", "tde", "color", "shape", "physics", "g
              "ecolor", "decline"]
 # what ``extract_all(sets=None)`` runs: the ten sets before the opt-in post-peak sets (ecolor, decline)
 DEFAULT_SETS = SET_NAMES[:10]
+# Extension sets: mask bits from len(SET_NAMES) on (LCFE_XSET_* of include/lcfe.h).  They are not part of SET_NAMES, of
+# lcfe_stats or of lcfe_implemented_mask(), so that adding one leaves the ABI of the numbered sets as it is; they run only
+# when named.
+EXT_SET_NAMES = ["advanced"]
+ALL_SET_NAMES = SET_NAMES + EXT_SET_NAMES
 
 _STAT17 = ["n_obs", "mean", "std", "min", "max", "median", "skew", "kurtosis", "amplitude", "mad",
            "iqr", "beyond_1std", "beyond_2std", "max_slope", "mean_snr", "time_span", "cadence_mean"]
@@ -167,13 +172,27 @@ def _decline():
     return cols
 
 
+def _advanced():
+    # advanced_features.py:507-620, in the order extract_advanced_features_single builds its dict
+    cols = [f"{b}_abs_mag_{k}" for b in "gri" for k in ("peak", "mean")]
+    mhps = ["mhps_10", "mhps_30", "mhps_100", "mhps_365", "mhps_ratio_10_100", "mhps_ratio_30_365"]
+    cols += [f"{b}_{k}" for b in "rg" for k in mhps]
+    cols += [f"{b}_fleet_{k}" for b in "rg" for k in ("width", "asymmetry", "chi2")]
+    cols += ["pre_peak_g_r_mean", "pre_peak_r_i_mean", "pre_peak_g_r_slope", "pre_peak_r_i_slope"]
+    cols += ["r_acf_10d", "r_acf_30d", "r_acf_ratio"]
+    cols += [f"{b}_early_late_{k}_ratio" for b in "gri" for k in ("flux", "var")]
+    hos = ["flux_skewness", "flux_kurtosis", "flux_biweight"]
+    cols += hos + [f"{b}_{k}" for b in "gr" for k in hos]
+    return cols + ["peak_lag_g_r", "peak_lag_r_i", "peak_flux_ratio_g_r", "peak_flux_ratio_r_i"]
+
+
 COLUMNS = {"stat": _stat(), "bazin": _bazin(), "powerlaw": _powerlaw(), "tde": _tde(),
            "color": _color(), "shape": _shape(), "physics": _physics(), "gp2d": _gp2d(), "gp1d": _gp1d(),
-           "research": _research(), "ecolor": _ecolor(), "decline": _decline()}
+           "research": _research(), "ecolor": _ecolor(), "decline": _decline(), "advanced": _advanced()}
 NCOLS = {k: len(v) for k, v in COLUMNS.items()}
 assert NCOLS == {"stat": 123, "bazin": 52, "powerlaw": 27, "tde": 25, "color": 83, "shape": 65,
                  "physics": 32, "gp2d": 27, "gp1d": 21, "research": 40, "ecolor": 45,
-                 "decline": 36}, NCOLS
+                 "decline": 36, "advanced": 50}, NCOLS
 
 # integer-valued columns of the statistics frame (int64 in the reference's DataFrame)
 STAT_INT_COLUMNS = [f"{p}_n_obs" for p in BANDS + ["all"]] + ["peak_band"]

@@ -12,11 +12,15 @@
 #include "research.hpp"
 #include "ecolor.hpp"
 #include "decline.hpp"
+#include "advanced.hpp"
 
 namespace lcfe {
 
 enum { SET_STAT = 0, SET_BAZIN, SET_POWERLAW, SET_TDE, SET_COLOR, SET_SHAPE, SET_PHYSICS, SET_GP2D, SET_GP1D, SET_RESEARCH, SET_ECOLOR,
        SET_DECLINE, NUM_SETS };
+// Extension sets: selected by the mask bits from NUM_SETS on, but not part of the public LCFE_NUM_SETS / lcfe_stats /
+// LCFE_MASK_ALL / lcfe_implemented_mask() (include/lcfe.h), so that adding one never changes the ABI of the numbered sets.
+enum { SET_ADVANCED = NUM_SETS, NUM_ALL_SETS };
 
 LCFE_HD int set_ncols(int set) {
     switch (set) {
@@ -32,6 +36,7 @@ LCFE_HD int set_ncols(int set) {
         case SET_RESEARCH: return 40;
         case SET_ECOLOR: return 45;
         case SET_DECLINE: return 36;
+        case SET_ADVANCED: return 50;
     }
     return 0;
 }
@@ -46,6 +51,7 @@ LCFE_HD int set_nstatus(int set) {
 #endif
         case SET_GP1D: return 4;
         case SET_RESEARCH: return 1;
+        case SET_ADVANCED: return 1;
     }
     return 0;
 }
@@ -108,6 +114,12 @@ template <int CAP>
 struct SetLds<SET_DECLINE, CAP> {
     ObjLds<CAP> obj;
     DeclineLds s;
+};
+
+template <int CAP>
+struct SetLds<SET_ADVANCED, CAP> {
+    ObjLds<CAP> obj;
+    AdvancedLds<CAP> s;
 };
 
 // copy `ncol` wave-shared doubles to the object's output row (coalesced on the device)
@@ -240,6 +252,18 @@ struct RunSet<W, SET_DECLINE, CAP> {
         store_row<W>(ws.s.out, row, DECLINE_NCOL);
         W::sync();
         return 0;
+    }
+};
+
+template <class W, int CAP>
+struct RunSet<W, SET_ADVANCED, CAP> {
+    static LCFE_FN int run(const ObjIn& in, SetLds<SET_ADVANCED, CAP>& ws, double* row, int32_t* st) {
+        stage_object<W, CAP>(in, ws.obj);
+        const int rc = advanced_object<W, CAP>(ws.obj, in.z, ws.s);
+        if (st && W::lane() == 0) st[0] = rc;
+        store_row<W>(ws.s.out, row, ADVANCED_NCOL);
+        W::sync();
+        return rc;
     }
 };
 

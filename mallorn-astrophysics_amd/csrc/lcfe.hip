@@ -1866,7 +1866,13 @@ int launch_stat(const BatchView& B, const Bins& bins, int64_t max_len, double* o
 
 #include "colnames.inc"
 
-bool set_implemented(int set) { return set >= 0 && set < NUM_SETS; }
+bool set_implemented(int set) { return set >= 0 && set < NUM_ALL_SETS; }
+
+// profile of the extension sets of the last call this thread made with prof != NULL (lcfe_last_ext_profile)
+thread_local double g_ext_ms[LCFE_NUM_XSETS];
+thread_local int32_t g_ext_launches[LCFE_NUM_XSETS];
+static_assert(NUM_SETS == LCFE_NUM_SETS && NUM_ALL_SETS == LCFE_NUM_SETS + LCFE_NUM_XSETS && SET_ADVANCED == LCFE_XSET_ADVANCED,
+              "set ids of feature_sets.hpp and include/lcfe.h");
 
 // Non-blocking side streams per device, created on first use and kept for the life of the process.
 constexpr int kSideStreams = 5;       // [0] Bazin, [1] decline fits, [2] streaming sets + GP tiers, [3], [4] further GP tiers
@@ -1954,23 +1960,39 @@ int lcfe_implemented_mask(void) {
     return m;
 }
 
+int lcfe_implemented_xmask(void) {
+    int m = 0;
+    for (int s = NUM_SETS; s < NUM_ALL_SETS; ++s)
+        if (set_implemented(s)) m |= 1 << s;
+    return m;
+}
+
+int lcfe_last_ext_profile(double* kernel_ms, int32_t* launches, int n) {
+    const int k = (n < LCFE_NUM_XSETS) ? ((n > 0) ? n : 0) : LCFE_NUM_XSETS;
+    for (int x = 0; x < k; ++x) {
+        if (kernel_ms) kernel_ms[x] = g_ext_ms[x];
+        if (launches) launches[x] = g_ext_launches[x];
+    }
+    return LCFE_NUM_XSETS;
+}
+
 int64_t lcfe_ncols(int mask) {
     int64_t n = 0;
-    for (int s = 0; s < NUM_SETS; ++s)
+    for (int s = 0; s < NUM_ALL_SETS; ++s)
         if (mask & (1 << s)) n += set_ncols(s);
     return n;
 }
 
 int64_t lcfe_nstatus(int mask) {
     int64_t n = 0;
-    for (int s = 0; s < NUM_SETS; ++s)
+    for (int s = 0; s < NUM_ALL_SETS; ++s)
         if (mask & (1 << s)) n += set_nstatus(s);
     return n;
 }
 
 const char* lcfe_colname(int mask, int64_t j) {
     if (j < 0) return nullptr;
-    for (int s = 0; s < NUM_SETS; ++s) {
+    for (int s = 0; s < NUM_ALL_SETS; ++s) {
         if (!(mask & (1 << s))) continue;
         if (j < set_ncols(s)) return kColNames[s][j];
         j -= set_ncols(s);
@@ -1981,7 +2003,7 @@ const char* lcfe_colname(int mask, int64_t j) {
 // workspace layout: [0, 1024) ticket counters (8 per set, room for 16 sets), [1024, 2048) bin counts, then the
 // kNumLists index lists of n_obj int32 each (256-byte aligned total), then the GP scratch slabs
 constexpr size_t kWsHeader = 2048;
-static_assert(NUM_SETS * 8 * sizeof(unsigned long long) <= 1024, "ticket counters of every set fit the header");
+static_assert(NUM_ALL_SETS * 8 * sizeof(unsigned long long) <= 1024, "ticket counters of every set fit the header");
 static size_t list_bytes(int64_t n_obj) {
     return (((size_t)(n_obj > 0 ? n_obj : 0) * kNumLists * sizeof(int)) + 255) & ~(size_t)255;
 }
@@ -2009,13 +2031,14 @@ static size_t long_bytes_of(int set, int64_t max_len) {
         case SET_RESEARCH: return kLongGrid * long_slab_bytes<SET_RESEARCH>();     // (an r band of more than 4096 days can sit in a short light curve)
         case SET_ECOLOR: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_ECOLOR>() : 0;
         case SET_DECLINE: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_DECLINE>() : 0;
+        case SET_ADVANCED: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_ADVANCED>() : 0;
     }
     return 0;
 }
 
 size_t lcfe_workspace_bytes_for(int mask, int64_t n_obj, int64_t n_points, int64_t max_len) {
     size_t b = lcfe_workspace_bytes(mask, n_obj, n_points);
-    for (int s = 0; s < NUM_SETS; ++s)
+    for (int s = 0; s < NUM_ALL_SETS; ++s)
         if (mask & (1 << s)) b += long_bytes_of(s, max_len);
     return b;
 }
@@ -2025,8 +2048,8 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
                         const double* d_err, const uint8_t* d_band, const double* d_z, double* d_out,
                         int32_t* d_status, void* d_workspace, size_t workspace_bytes, lcfe_stats* prof) {
     g_err.clear();
-    if (mask <= 0 || mask > LCFE_MASK_ALL) return fail_msg("lcfe_extract_device: empty or unknown feature-set mask");
-    for (int s = 0; s < NUM_SETS; ++s)
+    if (mask <= 0 || mask >= (1 << NUM_ALL_SETS)) return fail_msg("lcfe_extract_device: empty or unknown feature-set mask");
+    for (int s = 0; s < NUM_ALL_SETS; ++s)
         if ((mask & (1 << s)) && !set_implemented(s))
             return fail_msg("lcfe_extract_device: feature set " + std::to_string(s) + " is not built into this library");
     if (n_obj < 0 || n_points < 0 || max_len < 0) return fail_msg("lcfe_extract_device: negative size");
@@ -2049,6 +2072,7 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
     const int st_ld = (int)lcfe_nstatus(mask);
     if (prof) {
         memset(prof, 0, sizeof *prof);
+        for (int x = 0; x < LCFE_NUM_XSETS; ++x) { g_ext_ms[x] = 0; g_ext_launches[x] = 0; }
         prof->bytes_in = 25 * n_points + 8 * (n_obj + 1) + (d_z ? 8 * n_obj : 0);
         prof->bytes_out = 8 * n_obj * (int64_t)ld;
     }
@@ -2074,9 +2098,9 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
     double* gp1d_slab = (mask & (1 << SET_GP1D)) ? (double*)region : nullptr;
     if (gp1d_slab) region += kGp1dLongBytes;
     // the slabs of the long-object tier, when the workspace was sized with lcfe_workspace_bytes_for(.., max_len)
-    char* long_slab[NUM_SETS] = {};
+    char* long_slab[NUM_ALL_SETS] = {};
     if (workspace_bytes >= lcfe_workspace_bytes_for(mask, n_obj, n_points, max_len)) {
-        for (int s = 0; s < NUM_SETS; ++s) {
+        for (int s = 0; s < NUM_ALL_SETS; ++s) {
             const size_t lb = (mask & (1 << s)) ? long_bytes_of(s, max_len) : 0;
             if (lb) { long_slab[s] = region; region += lb; }
         }
@@ -2098,20 +2122,20 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
             case SET_BAZIN: return side[0];
             case SET_POWERLAW: return side[1];
             case SET_TDE: case SET_COLOR: case SET_SHAPE: case SET_PHYSICS: case SET_GP1D: case SET_RESEARCH:
-            case SET_ECOLOR: case SET_DECLINE: return side[2];
+            case SET_ECOLOR: case SET_DECLINE: case SET_ADVANCED: return side[2];
             default: return stream;
         }
     };
     // timing events (prof only): created once per host thread and device, reused by later calls -- a call with
     // `prof` drains the stream before it returns, so the events of the previous call are always complete
     struct Events {
-        hipEvent_t ev0[NUM_SETS] = {}, ev1[NUM_SETS] = {};
+        hipEvent_t ev0[NUM_ALL_SETS] = {}, ev1[NUM_ALL_SETS] = {};
         bool ready = false;
     };
     static thread_local Events pools[16];
     Events& E = pools[(dev >= 0 && dev < 16) ? dev : 0];
-    hipEvent_t (&ev0)[NUM_SETS] = E.ev0;
-    hipEvent_t (&ev1)[NUM_SETS] = E.ev1;
+    hipEvent_t (&ev0)[NUM_ALL_SETS] = E.ev0;
+    hipEvent_t (&ev1)[NUM_ALL_SETS] = E.ev1;
     // fork / join markers are short-lived: an event that was recorded is released by the runtime once the
     // recorded work has completed, so destroying it right after the wait was enqueued is safe
     struct Marker {
@@ -2120,12 +2144,12 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
     } fork_marker;
     hipEvent_t& forked = fork_marker.e;
     if (prof && !E.ready) {
-        for (int k = 0; k < NUM_SETS; ++k) { HIP_TRY(hipEventCreate(&ev0[k])); HIP_TRY(hipEventCreate(&ev1[k])); }
+        for (int k = 0; k < NUM_ALL_SETS; ++k) { HIP_TRY(hipEventCreate(&ev0[k])); HIP_TRY(hipEventCreate(&ev1[k])); }
         E.ready = true;
     }
     bool side_used[kSideStreams] = {false, false, false, false, false};
     int col0 = 0, st0 = 0, ne = 0;
-    for (int s = 0; s < NUM_SETS; ++s) {
+    for (int s = 0; s < NUM_ALL_SETS; ++s) {
         if (!(mask & (1 << s))) continue;
         if (ne == 0) {
             // shared prologue (timed with the first set): zero tickets and counts, bin the objects
@@ -2157,6 +2181,7 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
             case SET_RESEARCH: rc = launch_set<SET_RESEARCH>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
             case SET_ECOLOR: rc = launch_set<SET_ECOLOR>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
             case SET_DECLINE: rc = launch_set<SET_DECLINE>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
+            case SET_ADVANCED: rc = launch_set<SET_ADVANCED>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
             case SET_GP1D: rc = launch_gp1d(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, gp1d_slab, long_slab[s]); break;
             case SET_GP2D:
             {
@@ -2186,7 +2211,11 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
             }
         }
         if (rc) return rc;
-        if (prof) { HIP_TRY(hipEventRecord(ev1[s], q)); prof->launches[s] = nl; }
+        if (prof) {
+            HIP_TRY(hipEventRecord(ev1[s], q));
+            if (s < NUM_SETS) prof->launches[s] = nl;
+            else g_ext_launches[s - NUM_SETS] = nl;
+        }
         ++ne;
         col0 += set_ncols(s);
         st0 += set_nstatus(s);
@@ -2202,11 +2231,12 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
     }
     if (prof) {
         HIP_TRY(hipStreamSynchronize(stream));
-        for (int s = 0; s < NUM_SETS; ++s) {
+        for (int s = 0; s < NUM_ALL_SETS; ++s) {
             if (!(mask & (1 << s))) continue;
             float ms = 0;
             HIP_TRY(hipEventElapsedTime(&ms, ev0[s], ev1[s]));
-            prof->kernel_ms[s] = ms;
+            if (s < NUM_SETS) prof->kernel_ms[s] = ms;
+            else g_ext_ms[s - NUM_SETS] = ms;
         }
     }
     return 0;

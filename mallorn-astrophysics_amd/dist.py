@@ -23,21 +23,36 @@ COST_POINT = 4.8e-8
 COST_GP_N2 = 4.6e-10
 COST_GP_N3 = 5.1e-13
 GP_SETS = ("gp2d", "gp1d")
+# extension set "advanced": its Mexican-hat sums visit every pair of rows of the g band and of the r band (four divisions
+# and up to four exponentials in fp64 per pair).  Fitted to profiles/advanced_serial.json: 7.9 ms for the 111.6 M pairs of
+# the 125,000 bench objects, the rest of the set included.
+COST_ADV_PAIR = 7.1e-11
 
 
-def object_costs(offsets, sets=None):
-    """Predicted cost of every object for the feature sets `sets` (None = the full v34a/v55 workload)."""
-    n = np.diff(np.asarray(offsets, np.int64)).astype(np.float64)
+def object_costs(offsets, sets=None, band=None):
+    """Predicted cost of every object for the feature sets `sets` (None = the full v34a/v55 workload).  ``band``: the
+    batch's band codes, for the sets whose cost follows band lengths (without them an even split over six bands is
+    assumed)."""
+    offsets = np.asarray(offsets, np.int64)
+    n = np.diff(offsets).astype(np.float64)
     cost = COST_POINT * n
     if isinstance(sets, (int, np.integer)):                 # a feature-set mask, as mask_of / DeviceBatch.run accept
         from .engine import sets_of
         sets = sets_of(int(sets))
     if sets is None or any(s in GP_SETS for s in ([sets] if isinstance(sets, str) else sets)):
         cost = cost + COST_GP_N2 * n * n + COST_GP_N3 * n * n * n
+    if sets is not None and "advanced" in ([sets] if isinstance(sets, str) else sets):
+        if band is not None and len(band) == offsets[-1] and len(n):
+            band = np.asarray(band)
+            per = [np.add.reduceat((band == k).astype(np.float64), np.minimum(offsets[:-1], max(len(band) - 1, 0))) * (n > 0)
+                   if len(band) else np.zeros_like(n) for k in (1, 2)]
+        else:
+            per = [n / 6.0, n / 6.0]
+        cost = cost + COST_ADV_PAIR * 0.5 * (per[0] * per[0] + per[1] * per[1])
     return cost
 
 
-def shard_bounds(offsets, world: int, sets=None, cost=None):
+def shard_bounds(offsets, world: int, sets=None, cost=None, band=None):
     """Object index bounds [b_0=0, b_1, ..., b_world=n_obj] of ``world`` contiguous shards with (nearly) equal
     predicted COST: a N per object for the streaming sets and the bounded fits, plus c N^2 + b N^3 when a GP set
     is among ``sets`` -- the heavy N^3 tail of the Gram-matrix factorisations decides the slowest rank, not the
@@ -46,7 +61,7 @@ def shard_bounds(offsets, world: int, sets=None, cost=None):
     n_obj = len(offsets) - 1
     if n_obj <= 0:
         return np.zeros(world + 1, np.int64)
-    c = object_costs(offsets, sets) if cost is None else np.asarray(cost, np.float64)
+    c = object_costs(offsets, sets, band) if cost is None else np.asarray(cost, np.float64)
     cum = np.concatenate([[0.0], np.cumsum(c)])
     total = cum[-1]
     if total <= 0:                                          # all-empty objects: split by count
@@ -64,7 +79,7 @@ def shard_bounds(offsets, world: int, sets=None, cost=None):
 
 def shard_csr(csr, rank: int, world: int, z=None, sets=None):
     """The CSR slice (and redshifts) of ``rank``; ``(sub_csr, sub_z, (lo, hi))``."""
-    b = shard_bounds(csr["offsets"], world, sets)
+    b = shard_bounds(csr["offsets"], world, sets, band=csr.get("band"))
     lo, hi = int(b[rank]), int(b[rank + 1])
     off = np.asarray(csr["offsets"], np.int64)
     s, e = int(off[lo]), int(off[hi])
@@ -118,7 +133,7 @@ def extract_sharded(sets, csr, z=None, group=None, return_status=False):
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     n_obj = len(csr["offsets"]) - 1
-    bounds = shard_bounds(csr["offsets"], world, sets)
+    bounds = shard_bounds(csr["offsets"], world, sets, band=csr.get("band"))
     sub, sub_z, _ = shard_csr(csr, rank, world, z, sets)
     batch = DeviceBatch(sub, z=sub_z, device=torch.cuda.current_device())
     out, status = batch.run(sets)

@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .columns import COLUMNS, SET_NAMES
+from .columns import ALL_SET_NAMES, COLUMNS, EXT_SET_NAMES, SET_NAMES
 from .packing import check_csr
 
 
@@ -22,12 +22,13 @@ def mask_of(sets) -> int:
         sets = [sets]
     m = 0
     for s in sets:
-        m |= 1 << SET_NAMES.index(s)
+        m |= 1 << ALL_SET_NAMES.index(s)
     return m
 
 
 def sets_of(mask: int):
-    return [SET_NAMES[i] for i in range(len(SET_NAMES)) if mask >> i & 1]
+    """Names of the sets of a mask, core sets then extension sets: the order of their columns."""
+    return [ALL_SET_NAMES[i] for i in range(len(ALL_SET_NAMES)) if mask >> i & 1]
 
 
 def columns_of(mask: int):
@@ -35,6 +36,18 @@ def columns_of(mask: int):
     for s in sets_of(mask):
         cols += COLUMNS[s]
     return cols
+
+
+def _profile(st, mask):
+    """lcfe_stats as a dict; the extension sets of ``mask`` add their kernel time and launch count under ``ext``."""
+    prof = _lib.stats_to_dict(st)
+    if mask >> len(SET_NAMES):
+        nx = len(EXT_SET_NAMES)
+        ms, nl = (ctypes.c_double * nx)(), (ctypes.c_int32 * nx)()
+        _lib.load().lcfe_last_ext_profile(ms, nl, nx)
+        prof["ext"] = {name: {"kernel_ms": ms[k], "launches": nl[k]} for k, name in enumerate(EXT_SET_NAMES)
+                       if mask >> (len(SET_NAMES) + k) & 1}
+    return prof
 
 
 def _ptr(a, typ):
@@ -66,7 +79,7 @@ def extract_csr(sets, csr, z=None, device=-1, return_status=False, return_prof=F
     if return_status:
         res.append(status)
     if return_prof:
-        res.append(_lib.stats_to_dict(prof))
+        res.append(_profile(prof, mask))
     return res[0] if len(res) == 1 else tuple(res)
 
 
@@ -120,5 +133,5 @@ class DeviceBatch:
                                      ctypes.byref(st) if prof else None)
         _lib.check(rc, "lcfe_extract_device")
         if prof:
-            return out, status, _lib.stats_to_dict(st)
+            return out, status, _profile(st, mask)
         return out, status

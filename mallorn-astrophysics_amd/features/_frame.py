@@ -11,7 +11,7 @@ import warnings
 
 import numpy as np
 
-from ..columns import COLUMNS, DEFAULT_SETS, STAT_INT_COLUMNS, SET_NAMES
+from ..columns import ALL_SET_NAMES, COLUMNS, DEFAULT_SETS, STAT_INT_COLUMNS
 from ..engine import extract_csr, mask_of, sets_of
 from ..packing import pack_lightcurves
 
@@ -20,8 +20,9 @@ from ..packing import pack_lightcurves
 #   every other extractor appends the id last (colors.py:377, bazin_fitting.py:283, multiband_gp.py:381, ...)
 ID_FIRST = {"stat", "powerlaw"}
 INT_COLUMNS = {"stat": STAT_INT_COLUMNS}
-# sets that read the redshift column of the metadata (physics_based.py:481, research_features.py:552-559)
-NEEDS_Z = {"physics", "research"}
+# sets that read the redshift column of the metadata (physics_based.py:481, research_features.py:552-559,
+# advanced_features.py:647,662)
+NEEDS_Z = {"physics", "research", "advanced"}
 # sets whose reference batch function returns one row per REQUESTED id -- an id without rows gets the all-NaN row -- and
 # then fills every NaN with its column's median (enhanced_colors.py:236-260, time_to_decline.py:213-233)
 FILLED = {"ecolor", "decline"}
@@ -44,6 +45,9 @@ def _limit_message(set_name, csr, rows, lib):
             parts.append(f"{rest} with a band of more than {int(lib.lcfe_gp1d_max_points())} valid points")
         elif set_name == "research":
             parts.append(f"{rest} whose r band spans more than 65536 days (the Mexican-hat grid of the long-object tier)")
+        elif set_name == "advanced":
+            parts.append(f"{rest} whose r band spans more than 4194304 days (the autocorrelation's 1-day grid; only the "
+                         "three r_acf columns are NaN)")
         else:
             parts.append(f"{rest} beyond a tier limit")
     return ", ".join(parts)
@@ -55,7 +59,7 @@ def _warn_limits(names, csr, kept, status, lib):
     n = np.diff(csr["offsets"])
     st0 = 0
     for name in names:
-        nst = int(lib.lcfe_nstatus(1 << SET_NAMES.index(name)))
+        nst = int(lib.lcfe_nstatus(1 << ALL_SET_NAMES.index(name)))
         if nst:
             over = np.flatnonzero((status[:, st0:st0 + nst] == -100).any(axis=1))
             st0 += nst
@@ -126,7 +130,7 @@ def extract_all(lightcurves=None, metadata=None, object_ids=None, sets=None, csr
     ``lightcurves``: the long frame (``object_id, Time (MJD), Flux, Flux_err, Filter``), or pass ``csr=(csr, ids)``
     as ``utils.data_loader.load_lightcurves_csr`` / ``packing.pack_lightcurves`` return it (``object_ids`` then selects
     and orders objects of that batch).  ``sets``: names (default: the ten sets before the opt-in post-peak sets ``ecolor``
-    and ``decline``, which run only when named).  Returns ``{set name: DataFrame}`` with the reference's conventions per
+    and ``decline`` and the extension set ``advanced``, which run only when named).  Returns ``{set name: DataFrame}`` with the reference's conventions per
     extractor -- the post-peak frames have one row per requested id and are median-filled as the reference's are; with
     ``return_matrix`` also the raw, unfilled ``(matrix, status, kept_ids)``."""
     from .. import _lib
