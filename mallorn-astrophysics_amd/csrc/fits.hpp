@@ -124,14 +124,19 @@ LCFE_FN void bazin_finish(const double* t, const double* f, const double* e, int
     q[2] = np_clip(x[2], 0.1, 1e4);
     q[3] = np_clip(x[3], 0.1, 1e4);
     q[4] = np_clip(x[4], -1e6, 1e6);
-    double chi2 = 0;
+    constexpr int NS = row_slots<W>::value;
+    RowSum<W> cacc;
     BazinModel model;
-    for (int i = lane; i < m; i += W::LANES) {                     // :148-150
+    for (int i0 = lane; i0 < m; i0 += NS * W::LANES)               // :148-150
+#pragma unroll
+    for (int sl = 0; sl < NS; ++sl) {
+        const int i = i0 + sl * W::LANES;
+        if (i >= m) break;
         const double sg = (e[i] > 0) ? e[i] : 1.0;
         const double r = (f[i] - model(t[i], q)) / sg;
-        chi2 += r * r;
+        cacc[sl] += r * r;
     }
-    chi2 = W::sum(chi2);
+    const double chi2 = cacc.total();
     if (lane == 0) {
         out8[0] = q[0]; out8[1] = q[1]; out8[2] = q[2]; out8[3] = q[3]; out8[4] = q[4];
         out8[5] = np_clip(chi2 / (double)(m - 5), 0.0, 1e6);       // :151 (m == 5: x/0 -> inf -> 1e6)
@@ -299,9 +304,17 @@ LCFE_FN void decline_finish(const M& model, const double* tp, const double* fp, 
         if (lane == 0) *out = qnan();
         return;
     }
-    double ss = 0;
-    for (int i = lane; i < k; i += W::LANES) { const double r = fp[i] - model(tp[i], Z.x); ss += r * r; }   // :186-187
-    ss = W::sum(ss);
+    constexpr int NS = row_slots<W>::value;
+    RowSum<W> sacc;
+    for (int i0 = lane; i0 < k; i0 += NS * W::LANES)                 // :186-187
+#pragma unroll
+    for (int sl = 0; sl < NS; ++sl) {
+        const int i = i0 + sl * W::LANES;
+        if (i >= k) break;
+        const double r = fp[i] - model(tp[i], Z.x);
+        sacc[sl] += r * r;
+    }
+    const double ss = sacc.total();
     if (lane == 0) *out = (ss_tot > 0) ? 1.0 - ss / ss_tot : 0.0;       // :189
 }
 

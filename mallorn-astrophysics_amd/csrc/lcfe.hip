@@ -520,10 +520,21 @@ __global__ __launch_bounds__(kPlanThreads) void stat_plan_kernel(BatchView B, Bi
 // of its own fit by one phase per trip (trf.hpp: trf_outer / trf_inner) and takes the next fit from a device-side
 // ticket counter the moment its own is finished -- the groups of a wave never wait for each other.  The arithmetic of
 // a fit is exactly that of bazin_fit_band; only the schedule differs.
-constexpr int kFitTiers = 4;
-constexpr int kFitCaps[kFitTiers] = {32, 64, 128, 256};     // rows of one band
+//
+// Bands of up to 16 rows (tier 0) run on 4-lane groups, sixteen fits per wavefront: the trust-region algebra of a fit is
+// wave-uniform scalar work that every lane of its group repeats, so a group of half the width halves it per fit, and
+// wave.hpp's virtual lanes keep every sum in the order of the 8-lane group -- the results are bit-identical.  Tier 0 has
+// no launch of its own: the kernel of the 32-row tier serves both lists (see bazin_fit_kernel).
+constexpr int kFitTiers = 5;
+constexpr int kFitCaps[kFitTiers] = {16, 32, 64, 128, 256}; // rows of one band
 constexpr int kFitCountBase = 32;                           // counts[32 + t]: length of fit list t
-constexpr int kFitTicketBase = 96;                          // tickets[96 + t]
+// (the ticket counters of the fit lists sit behind those of the feature sets: 8 per set, 13 sets)
+constexpr int kFitTicketBase = 112;                         // tickets[112 + t]
+static_assert(kFitTicketBase >= NUM_ALL_SETS * 8, "fit tickets behind the sets' tickets");
+// tier of a band of m rows (m <= 256); narrow == 0 queues the bands of up to 16 rows on the 32-row list (LCFE_FIT_NARROW=0)
+__device__ __forceinline__ int fit_tier_of(int m, int narrow) {
+    return (m <= 16) ? (narrow ? 0 : 1) : ((m <= 32) ? 1 : ((m <= 64) ? 2 : ((m <= 128) ? 3 : 4)));
+}
 struct FitWs {
     double* pt;            // band-partitioned copies of t / flux / err, indexed like the CSR arrays
     double* pf;
@@ -540,13 +551,27 @@ struct FitRegion {
     double r[BCAP], rn[BCAP], w[BCAP];     // rn doubles as the key scratch of the median before the first trial point
     double A[6][BCAP + 5];
     double slot[2];
+    __device__ __forceinline__ double* trial() { return rn; }
+    __device__ __forceinline__ double* median_slot() { return slot; }
 };
+// The 16-row tier: sixteen of these must fit where eight FitRegion<32> do (20 KiB per wavefront, eight wavefronts per
+// CU), so two arrays share storage with matrix columns that are dead while they live.  The residual at the trial point
+// lies in the residual column A[5]: that column is written by trf_outer (from r) and last read when the QR hands over
+// Q^T f, the trial residual is written after that and copied to r before the next trf_outer.  The two words of the median
+// lie in A[4], which nothing uses before the first Jacobian.
+struct FitRegionNarrow {
+    double r[16], w[16];
+    double A[6][16 + 5];
+    __device__ __forceinline__ double* trial() { return A[5]; }
+    __device__ __forceinline__ double* median_slot() { return A[4]; }
+};
+static_assert(16 * sizeof(FitRegionNarrow) <= 8 * sizeof(FitRegion<32>), "the narrow regions fit the LDS of the 32-row tier");
 
 // partition pass: one object per wavefront (tier lists of the feature sets), up to `chunk` objects per ticket
 template <int CAP>
 __global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bins bins, int bin, int nan_from, FitWs F, double* out, int ld,
                                                                 int col0, int32_t* status, int st_ld, int st0,
-                                                                unsigned long long* ticket, int chunk) {
+                                                                unsigned long long* ticket, int chunk, int narrow) {
     __shared__ ObjLds<CAP> L;
     __shared__ long long next_ticket;
     __shared__ int loc[kFitTiers][64], nloc[kFitTiers], base_of[kFitTiers];
@@ -599,9 +624,9 @@ __global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bin
                     for (int q = 0; q < 8; ++q) o8[q] = qnan();
                     if (status) { status[i * (int64_t)st_ld + st0 + 2 * b] = TRF_FAIL_TOO_FEW; status[i * (int64_t)st_ld + st0 + 2 * b + 1] = 0; }
                 } else {
-                    const int tier = (m <= kFitCaps[0]) ? 0 : ((m <= kFitCaps[1]) ? 1 : ((m <= kFitCaps[2]) ? 2 : 3));
+                    const int tier = fit_tier_of(m, narrow);
                     const int slot = atomicAdd(&nloc[tier], 1);                 // LDS atomic: order inside a chunk is free
-                    loc[tier][slot] = (int)i * 8 + b;
+                    if (slot < 64) loc[tier][slot] = (int)i * 8 + b;
                 }
             }
             __syncthreads();
@@ -610,7 +635,8 @@ __global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bin
         if (threadIdx.x < kFitTiers) base_of[threadIdx.x] = nloc[threadIdx.x] ? atomicAdd(&bins.counts[kFitCountBase + threadIdx.x], nloc[threadIdx.x]) : 0;
         __syncthreads();
         for (int tr = 0; tr < kFitTiers; ++tr)
-            for (int q = threadIdx.x; q < nloc[tr]; q += 64) F.fits[tr * F.fit_stride + base_of[tr] + q] = loc[tr][q];
+            for (int q = threadIdx.x; q < nloc[tr] && q < 64; q += 64)
+                if (base_of[tr] + q < F.fit_stride) F.fits[tr * F.fit_stride + base_of[tr] + q] = loc[tr][q];
         __syncthreads();
     }
     nan_fill_bins<W>(bins, 0, nan_from, out, ld, col0, BAZIN_NCOL, status, st_ld, st0, 12);
@@ -622,21 +648,27 @@ template <int BCAP> struct fit_waves { static constexpr int N = (BCAP <= 32) ? 2
 // lane groups of a wave that take fits: all eight while their LDS regions fit next to each other, six in the 256-row tier
 template <int BCAP> struct fit_groups { static constexpr int N = (BCAP <= 128) ? 8 : 6; };
 
-template <int BCAP>
-__global__ __launch_bounds__(64, (fit_waves<BCAP>::N)) void bazin_fit_kernel(BatchView B, Bins bins, FitWs F, int tier, double* out, int ld, int col0,
-                                                            int32_t* status, int st_ld, int st0, unsigned long long* ticket) {
-    using G = GroupDev<8>;
-    constexpr int NG = fit_groups<BCAP>::N;
-    __shared__ FitRegion<BCAP> R[NG];
-    FitRegion<BCAP>& Rg = R[(G::group_id() < NG) ? G::group_id() : 0];
+// Blocks of a kernel that serves the 16-row list (4-lane groups) and the 32-row list (8-lane groups): the first
+// fit_narrow_first_blocks() blocks start on the 16-row list, the others on the 32-row list, and every block goes on to
+// the other list when the tickets of its own run out -- no block waits while either list has fits left, whatever the
+// split.  The split follows the work: a fit on a 4-lane group costs about 9/16 of one on an 8-lane group.
+__device__ __forceinline__ int fit_narrow_first_blocks(int count_narrow, int count_wide) {
+    const long long wn = 9ll * count_narrow, ww = 16ll * count_wide;
+    return (wn + ww > 0) ? (int)(((long long)gridDim.x * wn + (wn + ww) / 2) / (wn + ww)) : 0;
+}
+
+// the flat loop of one list: G = lane group of one fit, NG groups of the wave take fits, Region = their LDS regions
+template <class G, int NG, class Region>
+__device__ __forceinline__ void bazin_fit_loop(Region* R, const BatchView& B, const FitWs& F, const int* list, int count, double* out, int ld,
+                                               int col0, int32_t* status, int st_ld, int st0, unsigned long long* ticket) {
+    static_assert(NG <= G::NGROUPS, "one region per lane group");
+    Region& Rg = R[(G::group_id() < NG) ? G::group_id() : 0];
     TrfView<5> V;
 #pragma unroll
     for (int k = 0; k < 6; ++k) V.A[k] = Rg.A[k];
-    V.r = Rg.r; V.rn = Rg.rn; V.w = Rg.w;
-    const int count = bins.counts[kFitCountBase + tier];
-    const int* list = F.fits + (int64_t)tier * F.fit_stride;
+    V.r = Rg.r; V.rn = Rg.trial(); V.w = Rg.w;
     const int gl = G::lane();
-    const int leader = (int)(threadIdx.x & 63) & ~7;
+    const int leader = (int)(threadIdx.x & 63) & ~(G::LANES - 1);
     TrfState<5> Z;
     Z.phase = (G::group_id() < NG) ? FIT_IDLE : FIT_EXIT;
     int m = 0;
@@ -655,7 +687,7 @@ __global__ __launch_bounds__(64, (fit_waves<BCAP>::N)) void bazin_fit_kernel(Bat
                 const int b0 = F.pboff[obj * 8 + band];
                 m = F.pboff[obj * 8 + band + 1] - b0;
                 src = B.offsets[obj] + b0;
-                bazin_prepare<G, TrfView<5>>(F.pt + src, F.pf + src, F.pe + src, m, V, Rg.slot, reinterpret_cast<unsigned long long*>(Rg.rn), Z);
+                bazin_prepare<G, TrfView<5>>(F.pt + src, F.pf + src, F.pe + src, m, V, Rg.median_slot(), reinterpret_cast<unsigned long long*>(Rg.trial()), Z);
                 trf_begin<G, BazinModel, TrfView<5>>(BazinModel(), F.pt + src, F.pf + src, m, Z, V);
             }
         }
@@ -671,6 +703,33 @@ __global__ __launch_bounds__(64, (fit_waves<BCAP>::N)) void bazin_fit_kernel(Bat
             G::sync();
             Z.phase = FIT_IDLE;
         }
+    }
+}
+
+// list `tier` (bands of up to BCAP rows); the 32-row kernel also serves list 0 (up to 16 rows, 4-lane groups): a kernel
+// of its own behind the other four would add its longest fit to the end of the fit stream
+template <int BCAP>
+__global__ __launch_bounds__(64, (fit_waves<BCAP>::N)) void bazin_fit_kernel(BatchView B, Bins bins, FitWs F, int tier, double* out, int ld, int col0,
+                                                            int32_t* status, int st_ld, int st0, unsigned long long* ticket,
+                                                            unsigned long long* ticket_narrow) {
+    constexpr int NG = fit_groups<BCAP>::N;
+    const int count = bins.counts[kFitCountBase + tier];
+    const int* list = F.fits + (int64_t)tier * F.fit_stride;
+    if constexpr (BCAP == 32) {
+        __shared__ union Lds { FitRegion<32> wide[NG]; FitRegionNarrow narrow[16]; __device__ Lds() {} } R;
+        const int count_n = bins.counts[kFitCountBase];
+        const bool narrow_first = (int)blockIdx.x < fit_narrow_first_blocks(count_n, count);
+        for (int pass = 0; pass < 2; ++pass) {
+            if ((pass == 0) == narrow_first) {
+                if (count_n > 0) bazin_fit_loop<GroupDev<4>, 16>(R.narrow, B, F, F.fits, count_n, out, ld, col0, status, st_ld, st0, ticket_narrow);
+            } else {
+                if (count > 0) bazin_fit_loop<GroupDev<8>, NG>(R.wide, B, F, list, count, out, ld, col0, status, st_ld, st0, ticket);
+            }
+            __syncthreads();
+        }
+    } else {
+        __shared__ FitRegion<BCAP> R[NG];
+        bazin_fit_loop<GroupDev<8>, NG>(R, B, F, list, count, out, ld, col0, status, st_ld, st0, ticket);
     }
 }
 
@@ -690,8 +749,11 @@ __global__ __launch_bounds__(256) void bazin_cross_kernel(BatchView B, double* o
 // per object and band g/r/i, the post-peak rows (times relative to the peak, fluxes) and their peak flux and total
 // sum of squares, and queues the band's nine fits: the seven power laws (two parameters, the exponent is data) in
 // list A, the exponential and the linear model (three parameters) in list B, per tier of the post-peak row count.
-constexpr int kPlCountA = 40, kPlCountB = 44;               // counts[40 + t], counts[44 + t]
-constexpr int kPlTicketA = 104, kPlTicketB = 108;           // tickets[...]
+constexpr int kPlCountA = 40, kPlCountB = 48;               // counts[40 + t], counts[48 + t]
+constexpr int kPlTicketA = kFitTicketBase + kFitTiers, kPlTicketB = kPlTicketA + kFitTiers;     // tickets[...]
+static_assert(kFitCountBase >= kNumLists && kFitCountBase + kFitTiers <= kPlCountA && kPlCountA + kFitTiers <= kPlCountB && kPlCountB + kFitTiers <= 256,
+              "count slots of the fit lists");
+static_assert(kPlTicketB + kFitTiers <= 128, "ticket slots of the fit lists");
 struct PlWs {
     double* tp;            // post-peak times of band j of object i at offsets[i] + boff[j + 1] ..., indexed like the CSR arrays
     double* fp;
@@ -716,7 +778,7 @@ struct PlRegion {
 template <int CAP>
 __global__ __launch_bounds__(64, 2) void powerlaw_partition_kernel(BatchView B, Bins bins, int bin, int nan_from, PlWs F, double* out, int ld,
                                                                    int col0, int32_t* status, int st_ld, int st0,
-                                                                   unsigned long long* ticket, int chunk) {
+                                                                   unsigned long long* ticket, int chunk, int narrow) {
     __shared__ ObjLds<CAP> L;
     __shared__ long long next_ticket;
     using W = WaveDev;
@@ -773,12 +835,15 @@ __global__ __launch_bounds__(64, 2) void powerlaw_partition_kernel(BatchView B, 
                         if (status) { status[i * (int64_t)st_ld + st0 + 18 * j + 2 * id] = TRF_FAIL_TOO_FEW; status[i * (int64_t)st_ld + st0 + 18 * j + 2 * id + 1] = 0; }
                     }
                 } else {
-                    const int tier = (k <= kFitCaps[0]) ? 0 : ((k <= kFitCaps[1]) ? 1 : ((k <= kFitCaps[2]) ? 2 : 3));
+                    const int tier = fit_tier_of(k, narrow);
                     const int a0 = atomicAdd(&bins.counts[kPlCountA + tier], 7);
-                    for (int id = 0; id < 7; ++id) F.fitsA[tier * F.strideA + a0 + id] = (int)i * 32 + j * 9 + id;
+                    if (a0 + 7 <= F.strideA)
+                        for (int id = 0; id < 7; ++id) F.fitsA[tier * F.strideA + a0 + id] = (int)i * 32 + j * 9 + id;
                     const int b0 = atomicAdd(&bins.counts[kPlCountB + tier], 2);
-                    F.fitsB[tier * F.strideB + b0] = (int)i * 32 + j * 9 + 7;
-                    F.fitsB[tier * F.strideB + b0 + 1] = (int)i * 32 + j * 9 + 8;
+                    if (b0 + 2 <= F.strideB) {
+                        F.fitsB[tier * F.strideB + b0] = (int)i * 32 + j * 9 + 7;
+                        F.fitsB[tier * F.strideB + b0 + 1] = (int)i * 32 + j * 9 + 8;
+                    }
                 }
             }
             __syncthreads();
@@ -792,23 +857,18 @@ template <int N> struct pl_model;
 template <> struct pl_model<2> { using type = PowerModel; static __device__ __forceinline__ PowerModel make(int id) { return PowerModel{decline_exponent(id)}; } };
 template <> struct pl_model<3> { using type = Decline3Model; static __device__ __forceinline__ Decline3Model make(int id) { return Decline3Model{id}; } };
 
-template <int N, int BCAP>
-__global__ __launch_bounds__(64, (BCAP <= 64 ? 2 : 1)) void powerlaw_fit_kernel(BatchView B, Bins bins, PlWs F, int tier, double* out, int ld,
-                                                                                  int col0, int32_t* status, int st_ld, int st0,
-                                                                                  unsigned long long* ticket) {
-    using G = GroupDev<8>;
+template <class G, int N, int NG, class Region>
+__device__ __forceinline__ void powerlaw_fit_loop(Region* R, const BatchView& B, const PlWs& F, const int* list, int count, double* out, int ld,
+                                                  int col0, int32_t* status, int st_ld, int st0, unsigned long long* ticket) {
+    static_assert(NG <= G::NGROUPS, "one region per lane group");
     using M = typename pl_model<N>::type;
-    constexpr int NG = fit_groups<BCAP>::N;
-    __shared__ PlRegion<N, BCAP> R[NG];
-    PlRegion<N, BCAP>& Rg = R[(G::group_id() < NG) ? G::group_id() : 0];
+    Region& Rg = R[(G::group_id() < NG) ? G::group_id() : 0];
     TrfView<N> V;
 #pragma unroll
     for (int k = 0; k <= N; ++k) V.A[k] = Rg.A[k];
     V.r = Rg.r; V.rn = Rg.rn; V.w = Rg.w;
-    const int count = bins.counts[((N == 2) ? kPlCountA : kPlCountB) + tier];
-    const int* list = (N == 2) ? F.fitsA + (int64_t)tier * F.strideA : F.fitsB + (int64_t)tier * F.strideB;
     const int gl = G::lane();
-    const int leader = (int)(threadIdx.x & 63) & ~7;
+    const int leader = (int)(threadIdx.x & 63) & ~(G::LANES - 1);
     TrfState<N> Z;
     Z.phase = (G::group_id() < NG) ? FIT_IDLE : FIT_EXIT;
     M model = pl_model<N>::make(N == 2 ? 0 : 7);
@@ -829,7 +889,7 @@ __global__ __launch_bounds__(64, (BCAP <= 64 ? 2 : 1)) void powerlaw_fit_kernel(
                 k = F.kk[obj * 3 + j];
                 ss_tot = F.sstot[obj * 3 + j];
                 const int64_t src = B.offsets[obj] + F.pboff[obj * 8 + j + 1];
-                for (int i = gl; i < k; i += 8) { Rg.t[i] = F.tp[src + i]; Rg.f[i] = F.fp[src + i]; Rg.w[i] = 1.0; }
+                for (int i = gl; i < k; i += G::LANES) { Rg.t[i] = F.tp[src + i]; Rg.f[i] = F.fp[src + i]; Rg.w[i] = 1.0; }
                 model = pl_model<N>::make(id);
                 decline_setup<N>(id, F.peak[obj * 3 + j], Z);
                 G::sync();
@@ -848,6 +908,34 @@ __global__ __launch_bounds__(64, (BCAP <= 64 ? 2 : 1)) void powerlaw_fit_kernel(
             G::sync();
             Z.phase = FIT_IDLE;
         }
+    }
+}
+
+// list `tier` of the N-parameter models; the 32-row kernel also serves list 0 on 4-lane groups (see bazin_fit_kernel)
+template <int N, int BCAP>
+__global__ __launch_bounds__(64, (BCAP <= 64 ? 2 : 1)) void powerlaw_fit_kernel(BatchView B, Bins bins, PlWs F, int tier, double* out, int ld,
+                                                                                  int col0, int32_t* status, int st_ld, int st0,
+                                                                                  unsigned long long* ticket, unsigned long long* ticket_narrow) {
+    constexpr int NG = fit_groups<BCAP>::N;
+    constexpr int kCount = (N == 2) ? kPlCountA : kPlCountB;
+    const int count = bins.counts[kCount + tier];
+    const int* lists = (N == 2) ? F.fitsA : F.fitsB;
+    const int* list = lists + (int64_t)tier * ((N == 2) ? F.strideA : F.strideB);
+    if constexpr (BCAP == 32) {
+        __shared__ union Lds { PlRegion<N, 32> wide[NG]; PlRegion<N, 16> narrow[16]; __device__ Lds() {} } R;
+        const int count_n = bins.counts[kCount];
+        const bool narrow_first = (int)blockIdx.x < fit_narrow_first_blocks(count_n, count);
+        for (int pass = 0; pass < 2; ++pass) {
+            if ((pass == 0) == narrow_first) {
+                if (count_n > 0) powerlaw_fit_loop<GroupDev<4>, N, 16>(R.narrow, B, F, lists, count_n, out, ld, col0, status, st_ld, st0, ticket_narrow);
+            } else {
+                if (count > 0) powerlaw_fit_loop<GroupDev<8>, N, NG>(R.wide, B, F, list, count, out, ld, col0, status, st_ld, st0, ticket);
+            }
+            __syncthreads();
+        }
+    } else {
+        __shared__ PlRegion<N, BCAP> R[NG];
+        powerlaw_fit_loop<GroupDev<8>, N, NG>(R, B, F, list, count, out, ld, col0, status, st_ld, st0, ticket);
     }
 }
 
@@ -1553,6 +1641,12 @@ size_t bazin_ws_bytes(int64_t n_obj, int64_t n_points) {
     return ((3 * 8 * np + 255) & ~(size_t)255) + ((32 * no + 255) & ~(size_t)255) + ((4 * (size_t)kFitTiers * 6 * no + 255) & ~(size_t)255);
 }
 
+// LCFE_FIT_NARROW=0 queues the bands of up to 16 rows on the 32-row fit lists, as before the 16-row tier (A/B measurements)
+static bool fit_narrow_enabled() {
+    static const bool on = [] { const char* e = getenv("LCFE_FIT_NARROW"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
 template <int CAP>
 int launch_bazin_partition(const BatchView& B, const Bins& bins, int bin, int nan_from, const FitWs& F, double* out, int ld, int col0,
                            int32_t* status, int st_ld, int st0, hipStream_t stream, int dev, unsigned long long* ticket) {
@@ -1563,7 +1657,7 @@ int launch_bazin_partition(const BatchView& B, const Bins& bins, int bin, int na
     if (grid * 8 > B.n_obj) grid = (B.n_obj + 7) / 8;
     if (grid < 1) return 0;
     hipLaunchKernelGGL((bazin_partition_kernel<CAP>), dim3((unsigned)grid), dim3(64), 0, stream, B, bins, bin, nan_from, F, out, ld, col0,
-                       status, st_ld, st0, ticket, 8);
+                       status, st_ld, st0, ticket, 8, fit_narrow_enabled() ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1580,7 +1674,7 @@ static int fit_waves_cap(int bcap, int per_cu) {
 
 template <int BCAP>
 int launch_bazin_fits(const BatchView& B, const Bins& bins, const FitWs& F, int tier, double* out, int ld, int col0, int32_t* status,
-                      int st_ld, int st0, hipStream_t stream, int dev, unsigned long long* ticket) {
+                      int st_ld, int st0, hipStream_t stream, int dev, unsigned long long* ticket, unsigned long long* ticket_narrow) {
     int per_cu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bazin_fit_kernel<BCAP>, 64, 0));
     if (per_cu < 1) per_cu = 1;
@@ -1589,7 +1683,7 @@ int launch_bazin_fits(const BatchView& B, const Bins& bins, const FitWs& F, int 
     if (grid * 8 > 6 * B.n_obj) grid = (6 * B.n_obj + 7) / 8;
     if (grid < 1) return 0;
     hipLaunchKernelGGL((bazin_fit_kernel<BCAP>), dim3((unsigned)grid), dim3(64), 0, stream, B, bins, F, tier, out, ld, col0, status,
-                       st_ld, st0, ticket);
+                       st_ld, st0, ticket, ticket_narrow);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1632,10 +1726,12 @@ int launch_bazin(const BatchView& B, const Bins& bins, int64_t max_len, double* 
     int rc = launch_tier<SET_BAZIN, 1024>(B, bins, kBazinFallbackList, kNumBins, out, ld, col0, status, st_ld, st0, stream, dev, tk + 5, 32);
     if (rc) return rc;
     ++*n_launch;
-    rc = launch_bazin_fits<256>(B, bins, F, 3, out, ld, col0, status, st_ld, st0, stream, dev, tickets + kFitTicketBase + 3);
-    if (!rc) rc = launch_bazin_fits<128>(B, bins, F, 2, out, ld, col0, status, st_ld, st0, stream, dev, tickets + kFitTicketBase + 2);
-    if (!rc) rc = launch_bazin_fits<64>(B, bins, F, 1, out, ld, col0, status, st_ld, st0, stream, dev, tickets + kFitTicketBase + 1);
-    if (!rc) rc = launch_bazin_fits<32>(B, bins, F, 0, out, ld, col0, status, st_ld, st0, stream, dev, tickets + kFitTicketBase + 0);
+    // (the 32-row launch serves the 16-row list as well: tier 0 has no kernel of its own)
+    unsigned long long* ftk = tickets + kFitTicketBase;
+    rc = launch_bazin_fits<256>(B, bins, F, 4, out, ld, col0, status, st_ld, st0, stream, dev, ftk + 4, ftk);
+    if (!rc) rc = launch_bazin_fits<128>(B, bins, F, 3, out, ld, col0, status, st_ld, st0, stream, dev, ftk + 3, ftk);
+    if (!rc) rc = launch_bazin_fits<64>(B, bins, F, 2, out, ld, col0, status, st_ld, st0, stream, dev, ftk + 2, ftk);
+    if (!rc) rc = launch_bazin_fits<32>(B, bins, F, 1, out, ld, col0, status, st_ld, st0, stream, dev, ftk + 1, ftk);
     if (rc) return rc;
     *n_launch += 4;
     hipLaunchKernelGGL(bazin_cross_kernel, dim3((unsigned)((B.n_obj + 255) / 256)), dim3(256), 0, stream, B, out, ld, col0);
@@ -1666,14 +1762,14 @@ int launch_powerlaw_partition(const BatchView& B, const Bins& bins, int bin, int
     if (grid * 8 > B.n_obj) grid = (B.n_obj + 7) / 8;
     if (grid < 1) return 0;
     hipLaunchKernelGGL((powerlaw_partition_kernel<CAP>), dim3((unsigned)grid), dim3(64), 0, stream, B, bins, bin, nan_from, F, out, ld,
-                       col0, status, st_ld, st0, ticket, 8);
+                       col0, status, st_ld, st0, ticket, 8, fit_narrow_enabled() ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 template <int N, int BCAP>
 int launch_powerlaw_fits(const BatchView& B, const Bins& bins, const PlWs& F, int tier, double* out, int ld, int col0, int32_t* status,
-                         int st_ld, int st0, hipStream_t stream, int dev, unsigned long long* ticket) {
+                         int st_ld, int st0, hipStream_t stream, int dev, unsigned long long* ticket, unsigned long long* ticket_narrow) {
     int per_cu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (powerlaw_fit_kernel<N, BCAP>), 64, 0));
     if (per_cu < 1) per_cu = 1;
@@ -1683,7 +1779,7 @@ int launch_powerlaw_fits(const BatchView& B, const Bins& bins, const PlWs& F, in
     if (grid * 8 > nfit) grid = (nfit + 7) / 8;
     if (grid < 1) return 0;
     hipLaunchKernelGGL((powerlaw_fit_kernel<N, BCAP>), dim3((unsigned)grid), dim3(64), 0, stream, B, bins, F, tier, out, ld, col0, status,
-                       st_ld, st0, ticket);
+                       st_ld, st0, ticket, ticket_narrow);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1726,9 +1822,10 @@ int launch_powerlaw(const BatchView& B, const Bins& bins, int64_t max_len, doubl
     if (rc) return rc;
     ++*n_launch;
 #define PL_TIER(BC, T)                                                                                                        \
-    if (!rc) rc = launch_powerlaw_fits<2, BC>(B, bins, F, T, out, ld, col0, status, st_ld, st0, stream, dev, tickets + kPlTicketA + T); \
-    if (!rc) rc = launch_powerlaw_fits<3, BC>(B, bins, F, T, out, ld, col0, status, st_ld, st0, stream, dev, tickets + kPlTicketB + T);
-    PL_TIER(256, 3) PL_TIER(128, 2) PL_TIER(64, 1) PL_TIER(32, 0)
+    if (!rc) rc = launch_powerlaw_fits<2, BC>(B, bins, F, T, out, ld, col0, status, st_ld, st0, stream, dev, tickets + kPlTicketA + T, tickets + kPlTicketA); \
+    if (!rc) rc = launch_powerlaw_fits<3, BC>(B, bins, F, T, out, ld, col0, status, st_ld, st0, stream, dev, tickets + kPlTicketB + T, tickets + kPlTicketB);
+    // (the 32-row launches serve the 16-row lists as well: tier 0 has no kernels of its own)
+    PL_TIER(256, 4) PL_TIER(128, 3) PL_TIER(64, 2) PL_TIER(32, 1)
 #undef PL_TIER
     if (rc) return rc;
     *n_launch += 8;

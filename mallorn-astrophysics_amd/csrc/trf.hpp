@@ -502,9 +502,14 @@ struct trf_shared_terms<Model, decltype((void)Model::kSharedTerms)> { static con
 template <class W, class Model, class Store>
 LCFE_FN void trf_residual(const Model& model, const double* t, const double* y, int m, Store& S, const Vec<Model::NP>& xx,
                           double* out, double& cost2, bool& finite) {
-    double c = 0;
+    constexpr int NS = row_slots<W>::value;
+    RowSum<W> c;
     bool ok = true;
-    for (int i = W::lane(); i < m; i += W::LANES) {
+    for (int i0 = W::lane(); i0 < m; i0 += NS * W::LANES)
+#pragma unroll
+    for (int sl = 0; sl < NS; ++sl) {
+        const int i = i0 + sl * W::LANES;
+        if (i >= m) break;
         double mv;
         if constexpr (trf_shared_terms<Model>::value > 0) {
             // the terms of the model at xx stay in the first matrix columns (free between the QR and the next Jacobian)
@@ -520,9 +525,9 @@ LCFE_FN void trf_residual(const Model& model, const double* t, const double* y, 
         const double v = S.w[i] * (mv - y[i]);
         out[i] = v;
         ok = ok && finite_d(v);
-        c += v * v;
+        c[sl] += v * v;
     }
-    cost2 = W::sum(c);
+    cost2 = c.total();
     finite = W::all(ok);
 }
 
@@ -543,6 +548,7 @@ LCFE_FN double trf_fd_step(const Vec<N>& xx, const Vec<N>& lb, const Vec<N>& ub,
 template <class Model, class Store, int N, int K, int NT>
 LCFE_FN void trf_jacobian_row(const Model& model, double ti, double yi, double wi, double ri, int i, const Vec<N> (&x1)[N],
                               const double (&dx)[N], const double (&at_x)[NT], Store& S, double (&gacc)[N], bool& ok) {
+    // gacc: the partial sums of the virtual lane this row belongs to (RowSum slot)
     if constexpr (K < N) {
         const double f1 = wi * (model.template stepped<K>(ti, x1[K], at_x) - yi);
         const double jv = (f1 - ri) / dx[K];
@@ -560,7 +566,8 @@ LCFE_FN void trf_jacobian(const Model& model, const double* t, const double* y, 
     constexpr int N = Model::NP;
     const int lane = W::lane();
     bool ok = true;
-    double gacc[N];
+    constexpr int NS = row_slots<W>::value;
+    double gacc[NS][N];                  // [virtual lane of this lane][component]
     if constexpr (trf_shared_terms<Model>::value > 0) {
         // rows outside, components inside: the terms of the model that a step in component k does not touch are the
         // ones the residual evaluation at x left in the first matrix columns (same values, same arithmetic, same
@@ -574,14 +581,19 @@ LCFE_FN void trf_jacobian(const Model& model, const double* t, const double* y, 
             x1[k] = xx;
             x1[k][k] = xx[k] + h;
             dx[k] = x1[k][k] - xx[k];
-            gacc[k] = 0;
+#pragma unroll
+            for (int sl = 0; sl < NS; ++sl) gacc[sl][k] = 0;
         }
-        for (int i = lane; i < m; i += W::LANES) {
+        for (int i0 = lane; i0 < m; i0 += NS * W::LANES)
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) {
+            const int i = i0 + sl * W::LANES;
+            if (i >= m) break;
             const double ti = t[i], yi = y[i], wi = S.w[i], ri = S.r[i];
             double at_x[trf_shared_terms<Model>::value];
 #pragma unroll
             for (int k = 0; k < trf_shared_terms<Model>::value; ++k) at_x[k] = S.A[k][i];
-            trf_jacobian_row<Model, Store, N, 0>(model, ti, yi, wi, ri, i, x1, dx, at_x, S, gacc, ok);
+            trf_jacobian_row<Model, Store, N, 0>(model, ti, yi, wi, ri, i, x1, dx, at_x, S, gacc[sl], ok);
         }
     } else {
 #pragma unroll
@@ -590,19 +602,29 @@ LCFE_FN void trf_jacobian(const Model& model, const double* t, const double* y, 
             Vec<N> x1 = xx;
             x1[k] = xx[k] + h;
             const double dx = x1[k] - xx[k];
-            double ga = 0;
-            for (int i = lane; i < m; i += W::LANES) {
+            RowSum<W> ga;
+            for (int i0 = lane; i0 < m; i0 += NS * W::LANES)
+#pragma unroll
+            for (int sl = 0; sl < NS; ++sl) {
+                const int i = i0 + sl * W::LANES;
+                if (i >= m) break;
                 const double f1 = S.w[i] * (model(t[i], x1) - y[i]);
                 const double jv = (f1 - S.r[i]) / dx;
                 S.A[k][i] = jv;
                 ok = ok && finite_d(jv);
-                ga += jv * S.r[i];
+                ga[sl] += jv * S.r[i];
             }
-            gacc[k] = ga;
+#pragma unroll
+            for (int sl = 0; sl < NS; ++sl) gacc[sl][k] = ga[sl];
         }
     }
 #pragma unroll
-    for (int k = 0; k < N; ++k) g[k] = W::sum(gacc[k]);
+    for (int k = 0; k < N; ++k) {
+        RowSum<W> ga;
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) ga[sl] = gacc[sl][k];
+        g[k] = ga.total();
+    }
     finite = W::all(ok);
 }
 
@@ -662,6 +684,7 @@ LCFE_FN void trf_outer(int m, TrfState<Model::NP>& Z, Store& S) {
     constexpr int N = Model::NP;
     const int lane = W::lane();
     const int M = m + N;
+    constexpr int NS = row_slots<W>::value;
     const double gtol = 1e-8;
     TRF_T0();
     trf_cl_scaling<N>(Z);
@@ -705,10 +728,15 @@ LCFE_FN void trf_outer(int m, TrfState<Model::NP>& Z, Store& S) {
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         // norm of column k below (and including) row k, and its pivot element
-        double nn = 0;
-        for (int i = lane; i < M; i += W::LANES)
-            if (i >= k) { const double a = S.A[k][i]; nn += a * a; }
-        nn = W::sum(nn);
+        RowSum<W> nacc;
+        for (int i0 = lane; i0 < M; i0 += NS * W::LANES)
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) {
+            const int i = i0 + sl * W::LANES;
+            if (i >= M) break;
+            if (i >= k) { const double a = S.A[k][i]; nacc[sl] += a * a; }
+        }
+        const double nn = nacc.total();
         const double akk = S.A[k][k];
         const double nrm = sqrt(nn);
         const double alpha_h = (akk > 0) ? -nrm : nrm;
@@ -716,19 +744,22 @@ LCFE_FN void trf_outer(int m, TrfState<Model::NP>& Z, Store& S) {
         const double vtv = nn - 2.0 * alpha_h * akk + alpha_h * alpha_h;
         // dot products of v with the remaining columns (and the residual column)
         double dots[N + 1];
-#pragma unroll
-        for (int j = 0; j <= N; ++j) dots[j] = 0;
+        RowSum<W> dacc[N + 1];
         if (vtv > 0) {
-            for (int i = lane; i < M; i += W::LANES) {
+            for (int i0 = lane; i0 < M; i0 += NS * W::LANES)
+#pragma unroll
+            for (int sl = 0; sl < NS; ++sl) {
+                const int i = i0 + sl * W::LANES;
+                if (i >= M) break;
                 if (i < k) continue;
                 const double vi = (i == k) ? vk : S.A[k][i];
 #pragma unroll
                 for (int j = 0; j <= N; ++j)
-                    if (j > k) dots[j] += vi * S.A[j][i];
+                    if (j > k) dacc[j][sl] += vi * S.A[j][i];
             }
 #pragma unroll
             for (int j = 0; j <= N; ++j)
-                if (j > k) dots[j] = W::sum(dots[j]);
+                if (j > k) dots[j] = dacc[j].total();
             W::sync();
             for (int i = lane; i < M; i += W::LANES) {
                 if (i < k) continue;

@@ -151,10 +151,17 @@ struct LongDev : WaveDev {
 // work on other fits (the bands of one light curve).  Groups diverge freely: nothing here uses a
 // wave-wide collective or a hardware barrier.  Reductions are DPP moves inside an 8-lane group
 // (quad_perm swaps, then row_half_mirror) -- no LDS traffic.
+//
+// GS < 8: a narrow group that reproduces the arithmetic of the 8-lane one bit for bit.  Lane l stands for the VLANES =
+// 8 / GS virtual lanes l, l + GS, ... of an 8-lane group: a row loop written with RowSum (below) keeps one partial sum
+// per virtual lane (row i still belongs to virtual lane i mod 8), sum() adds the partial sums of ONE virtual lane each
+// over the physical lanes with the first DPP steps of the 8-lane pattern, and RowSum::total() combines the virtual
+// lanes in the order of the remaining steps.  max / min / any / all / ballot are order-free and cover the GS lanes.
 template <int GS>
 struct GroupDev {
-    static_assert(GS == 8, "DPP pattern below is written for 8-lane groups");
+    static_assert(GS == 8 || GS == 4 || GS == 2, "DPP patterns below: quad_perm swaps, then row_half_mirror");
     static constexpr int LANES = GS;
+    static constexpr int VLANES = 8 / GS;
     static constexpr int NGROUPS = 64 / GS;
     static constexpr int WAVE = 64;
     static constexpr int NWAVES = 1;
@@ -187,10 +194,11 @@ struct GroupDev {
     template <class V, class Op>
     static __device__ __forceinline__ V reduce(V v, Op op) {
         v = op(v, dpp<0xB1>(v));
-        v = op(v, dpp<0x4E>(v));
-        v = op(v, dpp<0x141>(v));
+        if constexpr (GS >= 4) v = op(v, dpp<0x4E>(v));
+        if constexpr (GS >= 8) v = op(v, dpp<0x141>(v));
         return v;
     }
+    // (GS < 8: the total over the physical lanes -- of one virtual lane's partial sums when called by RowSum::total())
     static __device__ __forceinline__ double sum(double v) { return reduce(v, [](double a, double b) { return a + b; }); }
     static __device__ __forceinline__ double max(double v) { return reduce(v, [](double a, double b) { return (b > a) ? b : a; }); }
     static __device__ __forceinline__ double min(double v) { return reduce(v, [](double a, double b) { return (b < a) ? b : a; }); }
@@ -344,6 +352,36 @@ __device__ __forceinline__ unsigned long long* phase_prof_lds() {
 #endif
 
 LCFE_FN int popcll(unsigned long long m) { return __builtin_popcountll(m); }
+
+// Row loops whose sums must not depend on the width of the lane group.  A policy may declare VLANES: the number of
+// virtual lanes each of its lanes stands for (GroupDev<4>: 2); every other policy has one.  The loops are written
+//     for (int i0 = W::lane(); i0 < m; i0 += NS * W::LANES)
+//         for (int sl = 0; sl < NS; ++sl) { const int i = i0 + sl * W::LANES; if (i >= m) break; acc[sl] += ...; }
+// with NS = row_slots<W>::value and a RowSum<W> acc: with NS = 1 that is the plain strided loop and W::sum.
+template <class W, class = void>
+struct row_slots { static constexpr int value = 1; };
+template <class W>
+struct row_slots<W, decltype((void)W::VLANES)> { static constexpr int value = W::VLANES; };
+
+template <class W>
+struct RowSum {
+    static constexpr int NS = row_slots<W>::value;
+    static_assert(NS == 1 || NS == 2 || NS == 4, "virtual lanes per lane");
+    double v[NS];
+    LCFE_FN RowSum() {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) v[s] = 0;
+    }
+    LCFE_FN double& operator[](int s) { return v[s]; }
+    LCFE_FN const double& operator[](int s) const { return v[s]; }
+    // the sum over all rows, uniform over the group: per virtual lane over the physical lanes first, then the virtual
+    // lanes pairwise -- together the order of the 8-lane DPP reduction
+    LCFE_FN double total() const {
+        if constexpr (NS == 1) return W::sum(v[0]);
+        else if constexpr (NS == 2) return W::sum(v[0]) + W::sum(v[1]);
+        else return (W::sum(v[0]) + W::sum(v[1])) + (W::sum(v[2]) + W::sum(v[3]));
+    }
+};
 
 // A value every lane of the wavefront holds (read from LDS, or a reduction result), made uniform for the compiler before
 // it steers control flow.  All lanes must be active.  Identity on the host.
