@@ -65,6 +65,20 @@ enum {
     LCFE_NUM_XSETS = 1
 };
 
+/* Registered sets.  Like the extension sets they are selected by LCFE_MASK(id) in any entry point, are in no table above and
+ * in neither implemented mask, and their columns and status words follow those of the extension sets in increasing id
+ * order.  Unlike them they are counted by no constant of this header: a caller finds them -- with every numbered and
+ * extension set -- through lcfe_set_count() / lcfe_set_info(), and reads their kernel times with lcfe_last_set_profile(), so
+ * a later set changes no value an existing caller may have compiled in.  Bit 13 is not assigned and never will be. */
+enum {
+    LCFE_RSET_CESIUM = 14,  /* cesium_features.py:311-414    80 columns (opt-in: per band Stetson J / K, beyond 1 / 2 sigma, flux
+                               percentile ratios, percent amplitude, maximum slope, weighted linear trend, Anderson-Darling;
+                               then the J consistency of g, r, i and the mean beyond-1-sigma share; no status words, no z) */
+    LCFE_RSET_FOURIER = 15  /* fourier_features.py:16-129    24 columns (opt-in: per band the dominant frequency, its power, the
+                               ratio to the mean power and the spectral entropy of the Hann-windowed band interpolated onto at
+                               most 128 equidistant times; the band's rows are taken in time order; no status words, no z) */
+};
+
 /* Per-call profile, filled when a non-NULL pointer is passed.  kernel_ms[s] is the HIP-event time
  * of feature set s's kernel(s) on the stream they were launched on.  The statistics set (with the
  * shared binning prologue) runs alone; the other sets run concurrently on internal side streams
@@ -155,6 +169,17 @@ int lcfe_implemented_xmask(void);
  * this THREAD made with prof != NULL: entry k belongs to extension set LCFE_NUM_SETS + k; sets that were not in that
  * call's mask read 0.  Fills min(n, LCFE_NUM_XSETS) entries of each non-NULL array and returns LCFE_NUM_XSETS. */
 int lcfe_last_ext_profile(double* kernel_ms, int32_t* launches, int n);
+
+
+/* The set registry: every set this build has -- numbered, extension and registered -- in increasing mask-bit order.
+ * lcfe_set_info describes entry k (0 <= k < lcfe_set_count()): its mask bit, its name (a static string), the number of its
+ * columns and of its status words, each through a pointer that may be NULL; it returns 0, or 1 when k is out of range. */
+int lcfe_set_count(void);
+int lcfe_set_info(int k, int* bit, const char** name, int* ncols, int* nstatus);
+/* kernel time (HIP events, ms) and launch count of the set with mask bit `bit` in the last lcfe_extract / lcfe_extract_device
+ * call this THREAD made with prof != NULL (0 for a set that was not in that call's mask); for a numbered set the values of
+ * lcfe_stats, for an extension set those of lcfe_last_ext_profile.  Returns 0, or 1 for a bit that is no set. */
+int lcfe_last_set_profile(int bit, double* kernel_ms, int32_t* launches);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LCFE_LIB_PATH") or os.path.join(_HERE, "csrc", "liblcfe.so")   # override: instrumented builds
-NUM_SETS = 12           # numbered sets (lcfe_stats); the extension sets are columns.EXT_SET_NAMES
+NUM_SETS = 12           # numbered sets (lcfe_stats); the extension sets are columns.EXT_SET_NAMES, the registered ones columns.REGISTERED_SETS
 
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_f64p = ctypes.POINTER(ctypes.c_double)
@@ -87,6 +87,12 @@ def load():
     lib.lcfe_implemented_xmask.restype = ctypes.c_int
     lib.lcfe_last_ext_profile.restype = ctypes.c_int
     lib.lcfe_last_ext_profile.argtypes = [c_f64p, c_i32p, ctypes.c_int]
+    lib.lcfe_set_count.restype = ctypes.c_int
+    lib.lcfe_set_info.restype = ctypes.c_int
+    lib.lcfe_set_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_char_p),
+                                  ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.lcfe_last_set_profile.restype = ctypes.c_int
+    lib.lcfe_last_set_profile.argtypes = [ctypes.c_int, c_f64p, c_i32p]
     lib.lcfe_workspace_bytes.restype = ctypes.c_size_t
     lib.lcfe_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int64]
     lib.lcfe_workspace_bytes_for.restype = ctypes.c_size_t
@@ -105,6 +111,18 @@ def load():
 def check(rc, what):
     if rc != 0:
         raise LcfeError(f"{what}: {load().lcfe_last_error().decode()}")
+
+
+def registry():
+    """The library's set registry (lcfe_set_count / lcfe_set_info): ``[(bit, name, ncols, nstatus)]`` in mask-bit order."""
+    lib = load()
+    rows = []
+    for k in range(lib.lcfe_set_count()):
+        bit, name, ncols, nstatus = ctypes.c_int(), ctypes.c_char_p(), ctypes.c_int(), ctypes.c_int()
+        if lib.lcfe_set_info(k, ctypes.byref(bit), ctypes.byref(name), ctypes.byref(ncols), ctypes.byref(nstatus)):
+            raise LcfeError(f"lcfe_set_info({k}) failed")
+        rows.append((bit.value, name.value.decode(), ncols.value, nstatus.value))
+    return rows
 
 
 def stats_to_dict(st: LcfeStats):

@@ -186,13 +186,36 @@ def _advanced():
     return cols + ["peak_lag_g_r", "peak_lag_r_i", "peak_flux_ratio_g_r", "peak_flux_ratio_r_i"]
 
 
+def _cesium():
+    # cesium_features.py:327-347 per band (:364-387), then the two cross-band columns (:398, :410)
+    per_band = ["stetson_j", "stetson_k", "beyond_1std", "beyond_2std", "flux_percentile_ratio_mid20",
+                "flux_percentile_ratio_mid35", "flux_percentile_ratio_mid50", "flux_percentile_ratio_mid65",
+                "flux_percentile_ratio_mid80", "percent_amplitude", "maximum_slope", "linear_trend", "anderson_darling"]
+    cols = [f"{b}_cesium_{k}" for b in BANDS for k in per_band]
+    return cols + ["cesium_stetson_j_consistency", "cesium_avg_beyond_1std"]
+
+
+def _fourier():
+    # fourier_features.py:117-120, bands in the order of :168
+    return [f"{b}_fourier_{k}" for b in BANDS for k in ("dominant_freq", "dominant_power", "power_ratio", "spectral_entropy")]
+
+
 COLUMNS = {"stat": _stat(), "bazin": _bazin(), "powerlaw": _powerlaw(), "tde": _tde(),
            "color": _color(), "shape": _shape(), "physics": _physics(), "gp2d": _gp2d(), "gp1d": _gp1d(),
-           "research": _research(), "ecolor": _ecolor(), "decline": _decline(), "advanced": _advanced()}
+           "research": _research(), "ecolor": _ecolor(), "decline": _decline(), "advanced": _advanced(), "cesium": _cesium(),
+           "fourier": _fourier()}
+# Registered sets: name -> mask bit, from bit 14 on (LCFE_RSET_* of include/lcfe.h; bit 13 is never assigned).  They are in
+# none of the name lists above and run only when named; the library lists them, with every other set, through
+# lcfe_set_count() / lcfe_set_info(), and the tests hold this table against that list entry by entry.  A later set is one
+# more line here.
+REGISTERED_SETS = {"cesium": 14, "fourier": 15}
+# every set by mask bit (the order of the columns of a multi-set call)
+SET_BITS = {**{name: bit for bit, name in enumerate(ALL_SET_NAMES)}, **REGISTERED_SETS}
+BIT_SETS = {bit: name for name, bit in SET_BITS.items()}
 NCOLS = {k: len(v) for k, v in COLUMNS.items()}
 assert NCOLS == {"stat": 123, "bazin": 52, "powerlaw": 27, "tde": 25, "color": 83, "shape": 65,
                  "physics": 32, "gp2d": 27, "gp1d": 21, "research": 40, "ecolor": 45,
-                 "decline": 36, "advanced": 50}, NCOLS
+                 "decline": 36, "advanced": 50, "cesium": 80, "fourier": 24}, NCOLS
 
 # integer-valued columns of the statistics frame (int64 in the reference's DataFrame)
 STAT_INT_COLUMNS = [f"{p}_n_obs" for p in BANDS + ["all"]] + ["peak_band"]

@@ -13,6 +13,8 @@
 #include "ecolor.hpp"
 #include "decline.hpp"
 #include "advanced.hpp"
+#include "cesium.hpp"
+#include "fourier.hpp"
 
 namespace lcfe {
 
@@ -20,7 +22,12 @@ enum { SET_STAT = 0, SET_BAZIN, SET_POWERLAW, SET_TDE, SET_COLOR, SET_SHAPE, SET
        SET_DECLINE, NUM_SETS };
 // Extension sets: selected by the mask bits from NUM_SETS on, but not part of the public LCFE_NUM_SETS / lcfe_stats /
 // LCFE_MASK_ALL / lcfe_implemented_mask() (include/lcfe.h), so that adding one never changes the ABI of the numbered sets.
-enum { SET_ADVANCED = NUM_SETS, NUM_ALL_SETS };
+// Registered sets follow from bit 14 on: they are in no table of include/lcfe.h but the registry (lcfe_set_count /
+// lcfe_set_info), so adding one changes no constant an older caller may hold.  Bit 13 stays unassigned for good: callers
+// rely on it being unknown.  NUM_ALL_SETS bounds the mask bits; set_known() tells which of them are sets.
+enum { SET_ADVANCED = NUM_SETS, SET_UNASSIGNED, SET_CESIUM, SET_FOURIER, NUM_ALL_SETS };
+static_assert(SET_UNASSIGNED == 13 && SET_CESIUM == 14 && SET_FOURIER == 15, "bit 13 is a hole; the registered sets start at 14");
+LCFE_HD bool set_known(int set) { return set >= 0 && set < NUM_ALL_SETS && set != SET_UNASSIGNED; }
 
 LCFE_HD int set_ncols(int set) {
     switch (set) {
@@ -37,6 +44,8 @@ LCFE_HD int set_ncols(int set) {
         case SET_ECOLOR: return 45;
         case SET_DECLINE: return 36;
         case SET_ADVANCED: return 50;
+        case SET_CESIUM: return 80;
+        case SET_FOURIER: return 24;
     }
     return 0;
 }
@@ -120,6 +129,17 @@ template <int CAP>
 struct SetLds<SET_ADVANCED, CAP> {
     ObjLds<CAP> obj;
     AdvancedLds<CAP> s;
+};
+
+template <int CAP>
+struct SetLds<SET_CESIUM, CAP> {
+    ObjLds<CAP> obj;
+    CesiumLds<CAP> s;
+};
+template <int CAP>
+struct SetLds<SET_FOURIER, CAP> {
+    ObjLds<CAP> obj;
+    FourierLds<CAP> s;
 };
 
 // copy `ncol` wave-shared doubles to the object's output row (coalesced on the device)
@@ -264,6 +284,27 @@ struct RunSet<W, SET_ADVANCED, CAP> {
         store_row<W>(ws.s.out, row, ADVANCED_NCOL);
         W::sync();
         return rc;
+    }
+};
+
+template <class W, int CAP>
+struct RunSet<W, SET_CESIUM, CAP> {
+    static LCFE_FN int run(const ObjIn& in, SetLds<SET_CESIUM, CAP>& ws, double* row, int32_t*) {
+        stage_object<W, CAP>(in, ws.obj);
+        cesium_object<W, CAP>(ws.obj, ws.s);
+        store_row<W>(ws.s.out, row, CESIUM_NCOL);
+        W::sync();
+        return 0;
+    }
+};
+template <class W, int CAP>
+struct RunSet<W, SET_FOURIER, CAP> {
+    static LCFE_FN int run(const ObjIn& in, SetLds<SET_FOURIER, CAP>& ws, double* row, int32_t*) {
+        stage_object<W, CAP>(in, ws.obj);
+        fourier_object<W, CAP>(ws.obj, ws.s);
+        store_row<W>(ws.s.out, row, FOURIER_NCOL);
+        W::sync();
+        return 0;
     }
 };
 

@@ -528,9 +528,10 @@ __global__ __launch_bounds__(kPlanThreads) void stat_plan_kernel(BatchView B, Bi
 constexpr int kFitTiers = 5;
 constexpr int kFitCaps[kFitTiers] = {16, 32, 64, 128, 256}; // rows of one band
 constexpr int kFitCountBase = 32;                           // counts[32 + t]: length of fit list t
-// (the ticket counters of the fit lists sit behind those of the feature sets: 8 per set, 13 sets)
+// (the ticket counters of the fit lists sit behind those of the numbered sets and the extension set: 8 per set, 13 sets;
+// the registered sets, bits 14 on, have theirs behind the bin counts -- set_ticket_base)
 constexpr int kFitTicketBase = 112;                         // tickets[112 + t]
-static_assert(kFitTicketBase >= NUM_ALL_SETS * 8, "fit tickets behind the sets' tickets");
+static_assert(kFitTicketBase >= (SET_ADVANCED + 1) * 8, "fit tickets behind the sets' tickets");
 // tier of a band of m rows (m <= 256); narrow == 0 queues the bands of up to 16 rows on the 32-row list (LCFE_FIT_NARROW=0)
 __device__ __forceinline__ int fit_tier_of(int m, int narrow) {
     return (m <= 16) ? (narrow ? 0 : 1) : ((m <= 32) ? 1 : ((m <= 64) ? 2 : ((m <= 128) ? 3 : 4)));
@@ -1560,6 +1561,12 @@ int launch_gp1d(const BatchView& B, const Bins& bins, int64_t max_len, double* o
     return 0;
 }
 
+// first of the 8 ticket counters of a set: tickets[8 s] up to the extension set; the registered sets (bits 14 on) continue
+// at tickets[256], behind the bin counts, because tickets[112..128) belong to the fit lists
+constexpr int kRegTicketBase = 256, kRegTicketSets = 4;
+constexpr int set_ticket_base(int set) { return (set <= SET_ADVANCED) ? set * 8 : kRegTicketBase + (set - SET_CESIUM) * 8; }
+static_assert(NUM_ALL_SETS - SET_CESIUM <= kRegTicketSets, "ticket counters of the registered sets");
+
 const int kTiers[] = {128, 256, 512, 1024, 2048};
 constexpr int kMaxPoints = 2048;
 
@@ -1610,7 +1617,7 @@ int launch_set(const BatchView& B, const Bins& bins, int64_t max_len, double* ou
     while (last < max_tier<SET>() && kTiers[last] < max_len) ++last;
     for (int ti = 0; ti <= last; ++ti) {
         const int nan_from = (ti == last) ? ti + 1 : kNumBins;
-        unsigned long long* tk = tickets + SET * 8 + ti;
+        unsigned long long* tk = tickets + set_ticket_base(SET) + ti;
         int rc = 0;
         switch (ti) {
             case 0: rc = launch_tier<SET, 128>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk); break;
@@ -1629,7 +1636,7 @@ int launch_set(const BatchView& B, const Bins& bins, int64_t max_len, double* ou
     // 4096 days of r band (its overflow list)
     if (long_slabs && (max_len > kTiers[max_tier<SET>()] || SET == SET_RESEARCH)) {
         const int rc = launch_long<SET>(B, bins, 6, (SET == SET_RESEARCH) ? 4 : -1, (SET == SET_RESEARCH) ? kResearchLongList : -1, out, ld, col0,
-                                        status, st_ld, st0, stream, tickets + SET * 8 + 7, long_slabs);
+                                        status, st_ld, st0, stream, tickets + set_ticket_base(SET) + 7, long_slabs);
         if (rc) return rc;
         ++*n_launch;
     }
@@ -1963,13 +1970,21 @@ int launch_stat(const BatchView& B, const Bins& bins, int64_t max_len, double* o
 
 #include "colnames.inc"
 
-bool set_implemented(int set) { return set >= 0 && set < NUM_ALL_SETS; }
+bool set_implemented(int set) { return set_known(set); }
 
-// profile of the extension sets of the last call this thread made with prof != NULL (lcfe_last_ext_profile)
-thread_local double g_ext_ms[LCFE_NUM_XSETS];
-thread_local int32_t g_ext_launches[LCFE_NUM_XSETS];
-static_assert(NUM_SETS == LCFE_NUM_SETS && NUM_ALL_SETS == LCFE_NUM_SETS + LCFE_NUM_XSETS && SET_ADVANCED == LCFE_XSET_ADVANCED,
+// names of the sets by mask bit (lcfe_set_info); the hole at bit 13 has none
+const char* const kSetNames[NUM_ALL_SETS] = {"stat", "bazin", "powerlaw", "tde", "color", "shape", "physics", "gp2d", "gp1d", "research",
+                                             "ecolor", "decline", "advanced", nullptr, "cesium", "fourier"};
+
+// profile of every set of the last call this thread made with prof != NULL (lcfe_last_set_profile; lcfe_last_ext_profile
+// reads the extension sets' entries)
+thread_local double g_set_ms[NUM_ALL_SETS];
+thread_local int32_t g_set_launches[NUM_ALL_SETS];
+// the numbered sets and the extension sets are exactly the public tables; everything above them is a registered set
+static_assert(NUM_SETS == LCFE_NUM_SETS && SET_ADVANCED == LCFE_XSET_ADVANCED && SET_ADVANCED + 1 == LCFE_NUM_SETS + LCFE_NUM_XSETS,
               "set ids of feature_sets.hpp and include/lcfe.h");
+static_assert(SET_CESIUM == LCFE_RSET_CESIUM && SET_FOURIER == LCFE_RSET_FOURIER && SET_UNASSIGNED == LCFE_NUM_SETS + LCFE_NUM_XSETS,
+              "registered set ids of feature_sets.hpp and include/lcfe.h; the bit after the extension sets stays unassigned");
 
 // Non-blocking side streams per device, created on first use and kept for the life of the process.
 constexpr int kSideStreams = 5;       // [0] Bazin, [1] decline fits, [2] streaming sets + GP tiers, [3], [4] further GP tiers
@@ -2059,16 +2074,41 @@ int lcfe_implemented_mask(void) {
 
 int lcfe_implemented_xmask(void) {
     int m = 0;
-    for (int s = NUM_SETS; s < NUM_ALL_SETS; ++s)
+    for (int s = NUM_SETS; s < NUM_SETS + LCFE_NUM_XSETS; ++s)
         if (set_implemented(s)) m |= 1 << s;
     return m;
+}
+
+int lcfe_set_count(void) {
+    int n = 0;
+    for (int s = 0; s < NUM_ALL_SETS; ++s) n += set_implemented(s) ? 1 : 0;
+    return n;
+}
+
+int lcfe_set_info(int k, int* bit, const char** name, int* ncols, int* nstatus) {
+    for (int s = 0; s < NUM_ALL_SETS; ++s) {
+        if (!set_implemented(s) || k-- != 0) continue;
+        if (bit) *bit = s;
+        if (name) *name = kSetNames[s];
+        if (ncols) *ncols = set_ncols(s);
+        if (nstatus) *nstatus = set_nstatus(s);
+        return 0;
+    }
+    return 1;
+}
+
+int lcfe_last_set_profile(int bit, double* kernel_ms, int32_t* launches) {
+    if (!set_implemented(bit)) return 1;
+    if (kernel_ms) *kernel_ms = g_set_ms[bit];
+    if (launches) *launches = g_set_launches[bit];
+    return 0;
 }
 
 int lcfe_last_ext_profile(double* kernel_ms, int32_t* launches, int n) {
     const int k = (n < LCFE_NUM_XSETS) ? ((n > 0) ? n : 0) : LCFE_NUM_XSETS;
     for (int x = 0; x < k; ++x) {
-        if (kernel_ms) kernel_ms[x] = g_ext_ms[x];
-        if (launches) launches[x] = g_ext_launches[x];
+        if (kernel_ms) kernel_ms[x] = g_set_ms[NUM_SETS + x];
+        if (launches) launches[x] = g_set_launches[NUM_SETS + x];
     }
     return LCFE_NUM_XSETS;
 }
@@ -2097,10 +2137,13 @@ const char* lcfe_colname(int mask, int64_t j) {
     return nullptr;
 }
 
-// workspace layout: [0, 1024) ticket counters (8 per set, room for 16 sets), [1024, 2048) bin counts, then the
-// kNumLists index lists of n_obj int32 each (256-byte aligned total), then the GP scratch slabs
-constexpr size_t kWsHeader = 2048;
-static_assert(NUM_ALL_SETS * 8 * sizeof(unsigned long long) <= 1024, "ticket counters of every set fit the header");
+// workspace layout: [0, 1024) ticket counters (8 per set up to the extension set, then the fit lists'), [1024, 2048) bin
+// counts, [2048, 2304) ticket counters of the registered sets (8 per set), then the kNumLists index lists of n_obj int32
+// each (256-byte aligned total), then the GP scratch slabs
+constexpr size_t kWsHeader = 2304;
+static_assert((SET_ADVANCED + 1) * 8 <= kFitTicketBase && kPlTicketB + kFitTiers <= 128, "ticket counters of the first 1024 bytes");
+static_assert(kRegTicketBase * sizeof(unsigned long long) == 2048 && (kRegTicketBase + kRegTicketSets * 8) * sizeof(unsigned long long) <= kWsHeader,
+              "ticket counters of the registered sets fit the header, behind the bin counts");
 static size_t list_bytes(int64_t n_obj) {
     return (((size_t)(n_obj > 0 ? n_obj : 0) * kNumLists * sizeof(int)) + 255) & ~(size_t)255;
 }
@@ -2129,6 +2172,8 @@ static size_t long_bytes_of(int set, int64_t max_len) {
         case SET_ECOLOR: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_ECOLOR>() : 0;
         case SET_DECLINE: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_DECLINE>() : 0;
         case SET_ADVANCED: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_ADVANCED>() : 0;
+        case SET_CESIUM: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_CESIUM>() : 0;
+        case SET_FOURIER: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_FOURIER>() : 0;
     }
     return 0;
 }
@@ -2169,7 +2214,7 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
     const int st_ld = (int)lcfe_nstatus(mask);
     if (prof) {
         memset(prof, 0, sizeof *prof);
-        for (int x = 0; x < LCFE_NUM_XSETS; ++x) { g_ext_ms[x] = 0; g_ext_launches[x] = 0; }
+        for (int s = 0; s < NUM_ALL_SETS; ++s) { g_set_ms[s] = 0; g_set_launches[s] = 0; }
         prof->bytes_in = 25 * n_points + 8 * (n_obj + 1) + (d_z ? 8 * n_obj : 0);
         prof->bytes_out = 8 * n_obj * (int64_t)ld;
     }
@@ -2219,7 +2264,7 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
             case SET_BAZIN: return side[0];
             case SET_POWERLAW: return side[1];
             case SET_TDE: case SET_COLOR: case SET_SHAPE: case SET_PHYSICS: case SET_GP1D: case SET_RESEARCH:
-            case SET_ECOLOR: case SET_DECLINE: case SET_ADVANCED: return side[2];
+            case SET_ECOLOR: case SET_DECLINE: case SET_ADVANCED: case SET_CESIUM: case SET_FOURIER: return side[2];
             default: return stream;
         }
     };
@@ -2279,6 +2324,8 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
             case SET_ECOLOR: rc = launch_set<SET_ECOLOR>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
             case SET_DECLINE: rc = launch_set<SET_DECLINE>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
             case SET_ADVANCED: rc = launch_set<SET_ADVANCED>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
+            case SET_CESIUM: rc = launch_set<SET_CESIUM>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
+            case SET_FOURIER: rc = launch_set<SET_FOURIER>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
             case SET_GP1D: rc = launch_gp1d(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, gp1d_slab, long_slab[s]); break;
             case SET_GP2D:
             {
@@ -2311,7 +2358,7 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
         if (prof) {
             HIP_TRY(hipEventRecord(ev1[s], q));
             if (s < NUM_SETS) prof->launches[s] = nl;
-            else g_ext_launches[s - NUM_SETS] = nl;
+            g_set_launches[s] = nl;
         }
         ++ne;
         col0 += set_ncols(s);
@@ -2333,7 +2380,7 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
             float ms = 0;
             HIP_TRY(hipEventElapsedTime(&ms, ev0[s], ev1[s]));
             if (s < NUM_SETS) prof->kernel_ms[s] = ms;
-            else g_ext_ms[s - NUM_SETS] = ms;
+            g_set_ms[s] = ms;
         }
     }
     return 0;

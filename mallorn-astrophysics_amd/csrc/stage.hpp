@@ -107,9 +107,10 @@ LCFE_FN void stage_object(const ObjIn& in, ObjLds<CAP>& L) {
 // whose [count_less, count_less_or_equal) interval contains r is written to sel[t] -- equal values
 // share an interval, so ties need no index tie-break.  The scan is register-blocked (4 own
 // elements per lane against 4 keys per trip) so that LDS reads are pipelined instead of exposing
-// one round trip per comparison.
-template <class W, int NT>
-LCFE_FN void wave_select_ranks(const double* x, int m, unsigned long long* keys, const int* ranks, double* sel) {
+// one round trip per comparison.  With RK the counts are kept too: rk[i] = #less + #less-or-equal of
+// every value (NaN last and all NaN equal), i.e. twice its mean rank minus one.
+template <class W, int NT, bool RK = false>
+LCFE_FN void wave_select_ranks(const double* x, int m, unsigned long long* keys, const int* ranks, double* sel, int* rk = nullptr) {
     const int lane = W::lane();
     for (int i = lane; i < m; i += W::LANES) keys[i] = sort_key(x[i]);
     W::sync();
@@ -141,6 +142,7 @@ LCFE_FN void wave_select_ranks(const double* x, int m, unsigned long long* keys,
         for (int c = 0; c < 4; ++c) {
             if (!own[c]) continue;
             const int i = base + c * W::LANES + lane;
+            if constexpr (RK) rk[i] = clt[c] + cle[c];
 #pragma unroll
             for (int t = 0; t < NT; ++t)
                 if (clt[c] <= ranks[t] && ranks[t] < cle[c]) sel[t] = x[i];

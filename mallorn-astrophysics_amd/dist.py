@@ -27,6 +27,14 @@ GP_SETS = ("gp2d", "gp1d")
 # and up to four exponentials in fp64 per pair).  Fitted to profiles/advanced_serial.json: 7.9 ms for the 111.6 M pairs of
 # the 125,000 bench objects, the rest of the set included.
 COST_ADV_PAIR = 7.1e-11
+# registered set "cesium": per row the Anderson-Darling term (a continued fraction of up to 374 fp64 divisions for the rows
+# beyond one sigma) and per pair of rows of a band one step of the rank scan; registered set "fourier": per band of at least
+# 10 rows a direct DFT of at most 63 bins x 128 samples.  ESTIMATES from operation counts (about 4 and 20 times the
+# streaming sets' cost per point at the bench's 28 rows per band), not yet fitted to a measurement: tools/ext_set_times.py
+# gives the serial kernel times to fit them to.
+COST_CESIUM_POINT = 2.0e-10
+COST_CESIUM_PAIR = 2.0e-12
+COST_FOURIER_BAND = 1.0e-9
 
 
 def object_costs(offsets, sets=None, band=None):
@@ -49,6 +57,17 @@ def object_costs(offsets, sets=None, band=None):
         else:
             per = [n / 6.0, n / 6.0]
         cost = cost + COST_ADV_PAIR * 0.5 * (per[0] * per[0] + per[1] * per[1])
+    names = [] if sets is None else ([sets] if isinstance(sets, str) else list(sets))
+    if "cesium" in names or "fourier" in names:
+        if band is not None and len(band) == offsets[-1] and len(n) and len(band):
+            band = np.asarray(band)
+            per = [np.add.reduceat((band == k).astype(np.float64), np.minimum(offsets[:-1], len(band) - 1)) * (n > 0) for k in range(6)]
+        else:
+            per = [n / 6.0] * 6
+        if "cesium" in names:
+            cost = cost + COST_CESIUM_POINT * n + COST_CESIUM_PAIR * sum(p * p for p in per)
+        if "fourier" in names:
+            cost = cost + COST_FOURIER_BAND * sum((p >= 10).astype(np.float64) for p in per)
     return cost
 
 

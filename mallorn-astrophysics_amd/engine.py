@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .columns import ALL_SET_NAMES, COLUMNS, EXT_SET_NAMES, SET_NAMES
+from .columns import BIT_SETS, COLUMNS, EXT_SET_NAMES, REGISTERED_SETS, SET_BITS, SET_NAMES
 from .packing import check_csr
 
 
@@ -22,13 +22,16 @@ def mask_of(sets) -> int:
         sets = [sets]
     m = 0
     for s in sets:
-        m |= 1 << ALL_SET_NAMES.index(s)
+        if s not in SET_BITS:
+            raise ValueError(f"unknown feature set {s!r} (known: {', '.join(SET_BITS)})")
+        m |= 1 << SET_BITS[s]
     return m
 
 
 def sets_of(mask: int):
-    """Names of the sets of a mask, core sets then extension sets: the order of their columns."""
-    return [ALL_SET_NAMES[i] for i in range(len(ALL_SET_NAMES)) if mask >> i & 1]
+    """Names of the sets of a mask in mask-bit order -- numbered sets, extension sets, registered sets: the order of their
+    columns."""
+    return [BIT_SETS[b] for b in sorted(BIT_SETS) if mask >> b & 1]
 
 
 def columns_of(mask: int):
@@ -39,9 +42,19 @@ def columns_of(mask: int):
 
 
 def _profile(st, mask):
-    """lcfe_stats as a dict; the extension sets of ``mask`` add their kernel time and launch count under ``ext``."""
+    """lcfe_stats as a dict; the extension sets of ``mask`` add their kernel time and launch count under ``ext``, the
+    registered sets theirs under ``registered``."""
     prof = _lib.stats_to_dict(st)
-    if mask >> len(SET_NAMES):
+    reg = {}
+    for name, bit in REGISTERED_SETS.items():
+        if mask >> bit & 1:
+            ms, nl = ctypes.c_double(), ctypes.c_int32()
+            if _lib.load().lcfe_last_set_profile(bit, ctypes.byref(ms), ctypes.byref(nl)):
+                raise _lib.LcfeError(f"lcfe_last_set_profile: bit {bit} is not a set of this library")
+            reg[name] = {"kernel_ms": ms.value, "launches": nl.value}
+    if reg:
+        prof["registered"] = reg
+    if mask >> len(SET_NAMES) & ((1 << len(EXT_SET_NAMES)) - 1):
         nx = len(EXT_SET_NAMES)
         ms, nl = (ctypes.c_double * nx)(), (ctypes.c_int32 * nx)()
         _lib.load().lcfe_last_ext_profile(ms, nl, nx)

@@ -2,3 +2,5 @@
 ``extract_all``: every feature set of a batch from one pack and one engine call."""
 from ._frame import extract_all  # noqa: F401
 from .advanced_features import extract_advanced_features  # noqa: F401
+from .cesium_features import extract_cesium_features  # noqa: F401
+from .fourier_features import extract_fourier_features  # noqa: F401

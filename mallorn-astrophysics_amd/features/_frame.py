@@ -11,14 +11,15 @@ import warnings
 
 import numpy as np
 
-from ..columns import ALL_SET_NAMES, COLUMNS, DEFAULT_SETS, STAT_INT_COLUMNS
+from ..columns import COLUMNS, DEFAULT_SETS, SET_BITS, STAT_INT_COLUMNS
 from ..engine import extract_csr, mask_of, sets_of
 from ..packing import pack_lightcurves
 
 # frame conventions of the reference's extractors: where ``object_id`` sits and which columns are int64
 #   statistical.py:214-226 (id first, *_n_obs / peak_band int64); train_v55_powerlaw.py:196-202 (dict with the id first);
 #   every other extractor appends the id last (colors.py:377, bazin_fitting.py:283, multiband_gp.py:381, ...)
-ID_FIRST = {"stat", "powerlaw"}
+#   fourier_features.py:156,166 (dict with the id first)
+ID_FIRST = {"stat", "powerlaw", "fourier"}
 INT_COLUMNS = {"stat": STAT_INT_COLUMNS}
 # sets that read the redshift column of the metadata (physics_based.py:481, research_features.py:552-559,
 # advanced_features.py:647,662)
@@ -26,6 +27,9 @@ NEEDS_Z = {"physics", "research", "advanced"}
 # sets whose reference batch function returns one row per REQUESTED id -- an id without rows gets the all-NaN row -- and
 # then fills every NaN with its column's median (enhanced_colors.py:236-260, time_to_decline.py:213-233)
 FILLED = {"ecolor", "decline"}
+# sets whose reference batch function returns one row per REQUESTED id as well, the all-NaN row for an id without rows, and
+# fills nothing (fourier_features.py:154-163)
+PER_REQUEST = {"fourier"}
 
 
 def _limit_message(set_name, csr, rows, lib):
@@ -59,7 +63,7 @@ def _warn_limits(names, csr, kept, status, lib):
     n = np.diff(csr["offsets"])
     st0 = 0
     for name in names:
-        nst = int(lib.lcfe_nstatus(1 << ALL_SET_NAMES.index(name)))
+        nst = int(lib.lcfe_nstatus(1 << SET_BITS[name]))
         if nst:
             over = np.flatnonzero((status[:, st0:st0 + nst] == -100).any(axis=1))
             st0 += nst
@@ -85,15 +89,11 @@ def frame_of(set_name, block, kept):
     return df
 
 
-def filled_frame(set_name, block, kept, requested):
-    """The frame of a FILLED set: one row per id of ``requested`` in request order (``kept`` is the subsequence of it
-    that has rows, repeats included; the others get the NaN row), then the reference's per-column median fill -- NaN
-    becomes the column's median, or 0.0 when the whole column is NaN -- and ``object_id`` last."""
-    import pandas as pd
-
-    cols = COLUMNS[set_name]
+def _rows_per_request(block, kept, requested, ncols):
+    """One row per id of ``requested`` in request order: ``kept`` is the subsequence of it that has rows, repeats
+    included; the others get the NaN row."""
     block = np.asarray(block, np.float64)
-    rows = np.full((len(requested), len(cols)), np.nan)
+    rows = np.full((len(requested), ncols), np.nan)
     j = 0
     for r, i in enumerate(requested):
         if j < len(kept) and kept[j] == i:
@@ -101,6 +101,22 @@ def filled_frame(set_name, block, kept, requested):
             j += 1
     if j != len(kept):
         raise ValueError("kept ids are not a subsequence of the requested ids")
+    return rows
+
+
+def per_request_frame(set_name, block, kept, requested):
+    """The frame of a PER_REQUEST set: one row per requested id, nothing filled, ``object_id`` where the set has it."""
+    return frame_of(set_name, _rows_per_request(block, kept, requested, len(COLUMNS[set_name])), list(requested))
+
+
+def filled_frame(set_name, block, kept, requested):
+    """The frame of a FILLED set: one row per id of ``requested`` in request order (``kept`` is the subsequence of it
+    that has rows, repeats included; the others get the NaN row), then the reference's per-column median fill -- NaN
+    becomes the column's median, or 0.0 when the whole column is NaN -- and ``object_id`` last."""
+    import pandas as pd
+
+    cols = COLUMNS[set_name]
+    rows = _rows_per_request(block, kept, requested, len(cols))
     df = pd.DataFrame(rows, columns=cols)
     df["object_id"] = list(requested)
     for col in cols:                                              # enhanced_colors.py:255-260, time_to_decline.py:228-233
@@ -130,7 +146,8 @@ def extract_all(lightcurves=None, metadata=None, object_ids=None, sets=None, csr
     ``lightcurves``: the long frame (``object_id, Time (MJD), Flux, Flux_err, Filter``), or pass ``csr=(csr, ids)``
     as ``utils.data_loader.load_lightcurves_csr`` / ``packing.pack_lightcurves`` return it (``object_ids`` then selects
     and orders objects of that batch).  ``sets``: names (default: the ten sets before the opt-in post-peak sets ``ecolor``
-    and ``decline`` and the extension set ``advanced``, which run only when named).  Returns ``{set name: DataFrame}`` with the reference's conventions per
+    and ``decline``, the extension set ``advanced`` and the registered sets ``cesium`` and ``fourier``, which run only when
+    named).  Returns ``{set name: DataFrame}`` with the reference's conventions per
     extractor -- the post-peak frames have one row per requested id and are median-filled as the reference's are; with
     ``return_matrix`` also the raw, unfilled ``(matrix, status, kept_ids)``."""
     from .. import _lib
@@ -161,6 +178,9 @@ def extract_all(lightcurves=None, metadata=None, object_ids=None, sets=None, csr
         if name in FILLED:
             requested = kept if object_ids is None else list(object_ids)
             frames[name] = filled_frame(name, out[:, col0:col0 + ncol], kept, requested)
+        elif name in PER_REQUEST:
+            requested = kept if object_ids is None else list(object_ids)
+            frames[name] = per_request_frame(name, out[:, col0:col0 + ncol], kept, requested)
         else:
             frames[name] = frame_of(name, out[:, col0:col0 + ncol], kept)
         col0 += ncol
