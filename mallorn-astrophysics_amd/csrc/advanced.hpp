@@ -460,4 +460,11 @@ LCFE_FN int advanced_object(const ObjLds<CAP>& L, double z, AdvancedLds<CAP>& S)
     return fits ? 0 : -100;
 }
 
+template <class W, class G, int CAP>   // RunSet's hook (feature_sets.hpp); G: policy of one per-band pass or fit
+LCFE_FN int run_object(const ObjLds<CAP>& L, const ObjIn& in, AdvancedLds<CAP>& S, int32_t* st) {
+    const int rc = advanced_object<W, CAP>(L, in.z, S);
+    if (st && W::lane() == 0) st[0] = rc;
+    return rc;
+}
+
 }  // namespace lcfe

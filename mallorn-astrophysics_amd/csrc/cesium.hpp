@@ -234,4 +234,7 @@ LCFE_FN void cesium_object(const ObjLds<CAP>& L, CesiumLds<CAP>& S) {
     W::sync();
 }
 
+template <class W, class G, int CAP>   // RunSet's hook (feature_sets.hpp); G: policy of one per-band pass or fit
+LCFE_FN int run_object(const ObjLds<CAP>& L, const ObjIn&, CesiumLds<CAP>& S, int32_t*) { cesium_object<W, CAP>(L, S); return 0; }
+
 }  // namespace lcfe

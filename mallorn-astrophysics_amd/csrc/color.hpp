@@ -192,4 +192,7 @@ LCFE_FN void color_object(const ObjLds<CAP>& L, ColorLds<CAP>& S) {
     W::sync();
 }
 
+template <class W, class G, int CAP>   // RunSet's hook (feature_sets.hpp); G: policy of one per-band pass or fit
+LCFE_FN int run_object(const ObjLds<CAP>& L, const ObjIn&, ColorLds<CAP>& S, int32_t*) { color_object<W, CAP>(L, S); return 0; }
+
 }  // namespace lcfe

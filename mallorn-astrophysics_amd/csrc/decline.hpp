@@ -86,4 +86,7 @@ LCFE_FN void decline_object(const ObjLds<CAP>& L, DeclineLds& S) {
     W::sync();
 }
 
+template <class W, class G, int CAP>   // RunSet's hook (feature_sets.hpp); G: policy of one per-band pass or fit
+LCFE_FN int run_object(const ObjLds<CAP>& L, const ObjIn&, DeclineLds& S, int32_t*) { decline_object<W, CAP>(L, S); return 0; }
+
 }  // namespace lcfe

@@ -191,4 +191,7 @@ LCFE_FN void ecolor_object(const ObjLds<CAP>& L, EcolorLds& S) {
     W::sync();
 }
 
+template <class W, class G, int CAP>   // RunSet's hook (feature_sets.hpp); G: policy of one per-band pass or fit
+LCFE_FN int run_object(const ObjLds<CAP>& L, const ObjIn&, EcolorLds& S, int32_t*) { ecolor_object<W, CAP>(L, S); return 0; }
+
 }  // namespace lcfe

@@ -15,6 +15,9 @@
 #include "advanced.hpp"
 #include "cesium.hpp"
 #include "fourier.hpp"
+#include "gp1d.hpp"
+
+#include <type_traits>
 
 namespace lcfe {
 
@@ -27,119 +30,83 @@ enum { SET_STAT = 0, SET_BAZIN, SET_POWERLAW, SET_TDE, SET_COLOR, SET_SHAPE, SET
 // rely on it being unknown.  NUM_ALL_SETS bounds the mask bits; set_known() tells which of them are sets.
 enum { SET_ADVANCED = NUM_SETS, SET_UNASSIGNED, SET_CESIUM, SET_FOURIER, NUM_ALL_SETS };
 static_assert(SET_UNASSIGNED == 13 && SET_CESIUM == 14 && SET_FOURIER == 15, "bit 13 is a hole; the registered sets start at 14");
-LCFE_HD bool set_known(int set) { return set >= 0 && set < NUM_ALL_SETS && set != SET_UNASSIGNED; }
-
-LCFE_HD int set_ncols(int set) {
-    switch (set) {
-        case SET_STAT: return 123;
-        case SET_BAZIN: return 52;
-        case SET_POWERLAW: return 27;
-        case SET_TDE: return 25;
-        case SET_COLOR: return 83;
-        case SET_SHAPE: return 65;
-        case SET_PHYSICS: return 32;
-        case SET_GP2D: return 27;
-        case SET_GP1D: return 21;
-        case SET_RESEARCH: return 40;
-        case SET_ECOLOR: return 45;
-        case SET_DECLINE: return 36;
-        case SET_ADVANCED: return 50;
-        case SET_CESIUM: return 80;
-        case SET_FOURIER: return 24;
-    }
-    return 0;
-}
-LCFE_HD int set_nstatus(int set) {
-    switch (set) {
-        case SET_BAZIN: return 12;
-        case SET_POWERLAW: return 54;
+// stream of a set when the call forks side streams (lcfe_extract_device): the caller's, or side stream 0, 1 or 2
+enum { STREAM_CALLER = -1, STREAM_SIDE0, STREAM_SIDE1, STREAM_SIDE2 };
 #ifdef LCFE_GP_PROF
-        case SET_GP2D: return 16;
+constexpr int GP_NSTATUS = 16;
 #else
-        case SET_GP2D: return 4;
+constexpr int GP_NSTATUS = 4;
 #endif
-        case SET_GP1D: return 4;
-        case SET_RESEARCH: return 1;
-        case SET_ADVANCED: return 1;
+
+// THE table of the sets: everything the library knows about a set beyond its arithmetic, one row per set.
+//   name, columns, status words: what lcfe_set_info reports
+//   working memory: the set's structure behind ObjLds<CAP> in SetLds (void: the GP sets have kernels of their own)
+//   tier:   largest LDS tier the working memory fits in (160 KiB per workgroup; 3 = 1024 rows, 4 = 2048 rows)
+//   chunk:  list entries per ticket (set_kernel): 1 for the heavy-tailed fits, 8 for the cheap streaming sets
+//   waves:  minimum waves per SIMD the 128-row tier's register allocation leaves room for: the bounded fits are long
+//           dependent fp64 chains, so a second wave per SIMD matters more than keeping every value in a register
+//   long:   light curves of more rows than this need the long-object tier
+//   stream: see above
+//   overflow: index list of the light curves a tier kernel hands to the long-object tier whatever their length (research:
+//           an r band of more days than the Mexican-hat grid in LDS; such a set always needs the long slabs), or -1
+#define LCFE_SET_TABLE(X)                                                                                                     \
+    /* id            name        columns         status        working memory     tier chunk waves long  stream    overflow */ \
+    X(SET_STAT,     "stat",     STAT_NCOL,      0,            StatScratch<CAP>,    4,  8,    1,   2048, STREAM_CALLER, -1)    \
+    X(SET_BAZIN,    "bazin",    BAZIN_NCOL,     12,           BazinLds<CAP>,       3,  1,    2,   1024, STREAM_SIDE0,  -1)    \
+    X(SET_POWERLAW, "powerlaw", POWERLAW_NCOL,  54,           PowerlawLds<CAP>,    3,  1,    2,   1024, STREAM_SIDE1,  -1)    \
+    X(SET_TDE,      "tde",      TDE_NCOL,       0,            TdeLds<CAP>,         4,  8,    1,   2048, STREAM_SIDE2,  -1)    \
+    X(SET_COLOR,    "color",    COLOR_NCOL,     0,            ColorLds<CAP>,       4,  8,    1,   2048, STREAM_SIDE2,  -1)    \
+    X(SET_SHAPE,    "shape",    SHAPE_NCOL,     0,            ShapeLds<CAP>,       4,  8,    1,   2048, STREAM_SIDE2,  -1)    \
+    X(SET_PHYSICS,  "physics",  PHYSICS_NCOL,   0,            PhysicsLds<CAP>,     4,  8,    1,   2048, STREAM_SIDE2,  -1)    \
+    X(SET_GP2D,     "gp2d",     GP_NCOL,        GP_NSTATUS,   void,               -1,  0,    0,   767,  STREAM_CALLER, -1)    \
+    X(SET_GP1D,     "gp1d",     GP1D_NCOL,      GP1D_NSTATUS, void,               -1,  0,    0,   767,  STREAM_SIDE2,  -1)    \
+    X(SET_RESEARCH, "research", RESEARCH_NCOL,  1,            ResearchLds<CAP>,    3,  8,    1,   1024, STREAM_SIDE2,  25)    \
+    X(SET_ECOLOR,   "ecolor",   ECOLOR_NCOL,    0,            EcolorLds,           4,  8,    1,   2048, STREAM_SIDE2,  -1)    \
+    X(SET_DECLINE,  "decline",  DECLINE_NCOL,   0,            DeclineLds,          4,  8,    1,   2048, STREAM_SIDE2,  -1)    \
+    X(SET_ADVANCED, "advanced", ADVANCED_NCOL,  1,            AdvancedLds<CAP>,    4,  8,    1,   2048, STREAM_SIDE2,  -1)    \
+    X(SET_CESIUM,   "cesium",   CESIUM_NCOL,    0,            CesiumLds<CAP>,      4,  8,    1,   2048, STREAM_SIDE2,  -1)    \
+    X(SET_FOURIER,  "fourier",  FOURIER_NCOL,   0,            FourierLds<CAP>,     4,  8,    1,   2048, STREAM_SIDE2,  -1)
+
+// rows of the LDS tiers 0..4 (lcfe.hip bins the light curves by them)
+constexpr int kTiers[] = {128, 256, 512, 1024, 2048};
+
+template <int SET> struct SetTraits;
+#define LCFE_SET_TRAITS(ID, NAME, NCOLS, NSTATUS, LDS, TIER, CHUNK, WAVES, LONG, STREAM, OVERFLOW)                                  \
+    template <> struct SetTraits<ID> {                                                                                        \
+        static constexpr const char* name = NAME;                                                                             \
+        static constexpr int ncols = NCOLS, nstatus = NSTATUS, max_tier = TIER, chunk = CHUNK, waves128 = WAVES;              \
+        static constexpr int long_above = LONG, stream = STREAM, overflow_list = OVERFLOW;                                    \
+        /* first of the set's 8 ticket counters: tickets[8 s] up to the extension set; the registered sets (bits 14 on)      \
+           continue at tickets[256], behind the bin counts, because tickets[112..128) belong to the fit lists */              \
+        static constexpr int ticket_base = (int(ID) <= SET_ADVANCED) ? ID * 8 : 256 + (ID - SET_CESIUM) * 8;                  \
+        static constexpr bool per_object = TIER >= 0;   /* runs through SetLds / RunSet */                                    \
+        template <int CAP> using Lds = LDS;                                                                                   \
+        static_assert(TIER < 0 || LONG == kTiers[TIER < 0 ? 0 : TIER], "the long-object tier starts where the LDS tiers end"); \
+    };
+LCFE_SET_TABLE(LCFE_SET_TRAITS)
+#undef LCFE_SET_TRAITS
+
+// a run-time set id as a compile-time tag: f(SetTag<SET>{}) of the set `set`, `unknown` for an id that is no set
+template <int SET> using SetTag = std::integral_constant<int, SET>;
+template <class F, class R = std::invoke_result_t<F&, SetTag<0>>>
+inline R for_set(int set, F&& f, R unknown = {}) {
+    switch (set) {
+#define LCFE_SET_CASE(ID, ...) case ID: return f(SetTag<ID>{});
+        LCFE_SET_TABLE(LCFE_SET_CASE)
+#undef LCFE_SET_CASE
     }
-    return 0;
+    return unknown;
 }
+inline bool set_known(int set) { return for_set(set, [](auto) { return true; }); }
+inline int set_ncols(int set) { return for_set(set, [](auto s) { return SetTraits<s()>::ncols; }); }
+inline int set_nstatus(int set) { return for_set(set, [](auto s) { return SetTraits<s()>::nstatus; }); }
+inline const char* set_name(int set) { return for_set(set, [](auto s) { return SetTraits<s()>::name; }); }
 
-// Wave-shared working memory (LDS on the device) of one object, per feature set.
+// Wave-shared working memory (LDS on the device) of one object: the staged rows, then the set's own structure.
 template <int SET, int CAP>
-struct SetLds;
-
-template <int CAP>
-struct SetLds<SET_STAT, CAP> {
+struct SetLds {
     ObjLds<CAP> obj;
-    StatScratch<CAP> stat;
-};
-
-template <int CAP>
-struct SetLds<SET_BAZIN, CAP> {
-    ObjLds<CAP> obj;
-    BazinLds<CAP> fit;
-};
-
-template <int CAP>
-struct SetLds<SET_POWERLAW, CAP> {
-    ObjLds<CAP> obj;
-    PowerlawLds<CAP> fit;
-};
-
-template <int CAP>
-struct SetLds<SET_TDE, CAP> {
-    ObjLds<CAP> obj;
-    TdeLds<CAP> s;
-};
-template <int CAP>
-struct SetLds<SET_COLOR, CAP> {
-    ObjLds<CAP> obj;
-    ColorLds<CAP> s;
-};
-template <int CAP>
-struct SetLds<SET_SHAPE, CAP> {
-    ObjLds<CAP> obj;
-    ShapeLds<CAP> s;
-};
-template <int CAP>
-struct SetLds<SET_PHYSICS, CAP> {
-    ObjLds<CAP> obj;
-    PhysicsLds<CAP> s;
-};
-
-template <int CAP>
-struct SetLds<SET_RESEARCH, CAP> {
-    ObjLds<CAP> obj;
-    ResearchLds<CAP> s;
-};
-
-template <int CAP>
-struct SetLds<SET_ECOLOR, CAP> {
-    ObjLds<CAP> obj;
-    EcolorLds s;
-};
-template <int CAP>
-struct SetLds<SET_DECLINE, CAP> {
-    ObjLds<CAP> obj;
-    DeclineLds s;
-};
-
-template <int CAP>
-struct SetLds<SET_ADVANCED, CAP> {
-    ObjLds<CAP> obj;
-    AdvancedLds<CAP> s;
-};
-
-template <int CAP>
-struct SetLds<SET_CESIUM, CAP> {
-    ObjLds<CAP> obj;
-    CesiumLds<CAP> s;
-};
-template <int CAP>
-struct SetLds<SET_FOURIER, CAP> {
-    ObjLds<CAP> obj;
-    FourierLds<CAP> s;
+    typename SetTraits<SET>::template Lds<CAP> s;
 };
 
 // copy `ncol` wave-shared doubles to the object's output row (coalesced on the device)
@@ -152,9 +119,6 @@ LCFE_FN void fill_row_nan(double* row, int ncol) {
     for (int k = W::lane(); k < ncol; k += W::LANES) row[k] = qnan();
 }
 
-template <class W, int SET, int CAP>
-struct RunSet;
-
 // policy of one bounded fit inside a wave: on the device the six band fits of a light curve run
 // side by side in 8-lane groups; the host simulation runs them one after the other
 template <class W> struct FitPolicy { using type = W; };
@@ -162,148 +126,51 @@ template <class W> struct FitPolicy { using type = W; };
 template <> struct FitPolicy<WaveDev> { using type = GroupDev<8>; };
 #endif
 
+// One object of a per-object set: stage, compute (the run_object hook next to the set's code), store the row.
+template <class W, int SET, int CAP>
+struct RunSet {
+    static LCFE_FN int run(const ObjIn& in, SetLds<SET, CAP>& ws, double* row, int32_t* st) {
+        stage_object<W, CAP>(in, ws.obj);
+        const int rc = run_object<W, typename FitPolicy<W>::type>(ws.obj, in, ws.s, st);
+        store_row<W>(ws.s.out, row, SetTraits<SET>::ncols);
+        W::sync();
+        return rc;
+    }
+};
 
-
+// The sets with launchers of their own keep their own forms: the fits take the group policy first and the status words
+// (written this way the register allocation of their kernels is what it was), the statistics set has its phase probes.
+template <class W, int CAP>
+struct RunSet<W, SET_BAZIN, CAP> {
+    static LCFE_FN int run(const ObjIn& in, SetLds<SET_BAZIN, CAP>& ws, double* row, int32_t* st) {
+        stage_object<W, CAP>(in, ws.obj);
+        bazin_object<typename FitPolicy<W>::type, W, CAP>(ws.obj, ws.s, st);
+        store_row<W>(ws.s.out, row, BAZIN_NCOL);
+        W::sync();
+        return 0;
+    }
+};
+template <class W, int CAP>
+struct RunSet<W, SET_POWERLAW, CAP> {
+    static LCFE_FN int run(const ObjIn& in, SetLds<SET_POWERLAW, CAP>& ws, double* row, int32_t* st) {
+        stage_object<W, CAP>(in, ws.obj);
+        powerlaw_object<typename FitPolicy<W>::type, W, CAP>(ws.obj, ws.s, st);
+        store_row<W>(ws.s.out, row, POWERLAW_NCOL);
+        W::sync();
+        return 0;
+    }
+};
 template <class W, int CAP>
 struct RunSet<W, SET_STAT, CAP> {
     static LCFE_FN int run(const ObjIn& in, SetLds<SET_STAT, CAP>& ws, double* row, int32_t*) {
         LCFE_PT0();
         stage_object<W, CAP>(in, ws.obj);
         LCFE_PT(0);
-        stat_object<W, typename FitPolicy<W>::type, CAP>(ws.obj, ws.stat);
+        stat_object<W, typename FitPolicy<W>::type, CAP>(ws.obj, ws.s);
         LCFE_PT0B();
-        store_row<W>(ws.stat.out, row, STAT_NCOL);
+        store_row<W>(ws.s.out, row, STAT_NCOL);
         W::sync();
         LCFE_PT(3);
-        return 0;
-    }
-};
-
-template <class W, int CAP>
-struct RunSet<W, SET_BAZIN, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_BAZIN, CAP>& ws, double* row, int32_t* st) {
-        stage_object<W, CAP>(in, ws.obj);
-        bazin_object<typename FitPolicy<W>::type, W, CAP>(ws.obj, ws.fit, st);
-        store_row<W>(ws.fit.out, row, BAZIN_NCOL);
-        W::sync();
-        return 0;
-    }
-};
-
-template <class W, int CAP>
-struct RunSet<W, SET_POWERLAW, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_POWERLAW, CAP>& ws, double* row, int32_t* st) {
-        stage_object<W, CAP>(in, ws.obj);
-        powerlaw_object<typename FitPolicy<W>::type, W, CAP>(ws.obj, ws.fit, st);
-        store_row<W>(ws.fit.out, row, POWERLAW_NCOL);
-        W::sync();
-        return 0;
-    }
-};
-
-template <class W, int CAP>
-struct RunSet<W, SET_TDE, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_TDE, CAP>& ws, double* row, int32_t*) {
-        stage_object<W, CAP>(in, ws.obj);
-        tde_object<W, CAP>(ws.obj, ws.s);
-        store_row<W>(ws.s.out, row, TDE_NCOL);
-        W::sync();
-        return 0;
-    }
-};
-template <class W, int CAP>
-struct RunSet<W, SET_COLOR, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_COLOR, CAP>& ws, double* row, int32_t*) {
-        stage_object<W, CAP>(in, ws.obj);
-        color_object<W, CAP>(ws.obj, ws.s);
-        store_row<W>(ws.s.out, row, COLOR_NCOL);
-        W::sync();
-        return 0;
-    }
-};
-template <class W, int CAP>
-struct RunSet<W, SET_SHAPE, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_SHAPE, CAP>& ws, double* row, int32_t*) {
-        stage_object<W, CAP>(in, ws.obj);
-        shape_object<W, typename FitPolicy<W>::type, CAP>(ws.obj, ws.s);
-        store_row<W>(ws.s.out, row, SHAPE_NCOL);
-        W::sync();
-        return 0;
-    }
-};
-template <class W, int CAP>
-struct RunSet<W, SET_PHYSICS, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_PHYSICS, CAP>& ws, double* row, int32_t*) {
-        stage_object<W, CAP>(in, ws.obj);
-        physics_object<W, CAP>(ws.obj, in.z, ws.s);
-        store_row<W>(ws.s.out, row, PHYSICS_NCOL);
-        W::sync();
-        return 0;
-    }
-};
-
-template <class W, int CAP>
-struct RunSet<W, SET_RESEARCH, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_RESEARCH, CAP>& ws, double* row, int32_t* st) {
-        stage_object<W, CAP>(in, ws.obj);
-        const int rc = research_object<W, CAP>(ws.obj, in.z, ws.s);
-        if (st && W::lane() == 0) st[0] = rc;
-        store_row<W>(ws.s.out, row, RESEARCH_NCOL);
-        W::sync();
-        return rc;
-    }
-};
-
-template <class W, int CAP>
-struct RunSet<W, SET_ECOLOR, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_ECOLOR, CAP>& ws, double* row, int32_t*) {
-        stage_object<W, CAP>(in, ws.obj);
-        ecolor_object<W, CAP>(ws.obj, ws.s);
-        store_row<W>(ws.s.out, row, ECOLOR_NCOL);
-        W::sync();
-        return 0;
-    }
-};
-template <class W, int CAP>
-struct RunSet<W, SET_DECLINE, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_DECLINE, CAP>& ws, double* row, int32_t*) {
-        stage_object<W, CAP>(in, ws.obj);
-        decline_object<W, CAP>(ws.obj, ws.s);
-        store_row<W>(ws.s.out, row, DECLINE_NCOL);
-        W::sync();
-        return 0;
-    }
-};
-
-template <class W, int CAP>
-struct RunSet<W, SET_ADVANCED, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_ADVANCED, CAP>& ws, double* row, int32_t* st) {
-        stage_object<W, CAP>(in, ws.obj);
-        const int rc = advanced_object<W, CAP>(ws.obj, in.z, ws.s);
-        if (st && W::lane() == 0) st[0] = rc;
-        store_row<W>(ws.s.out, row, ADVANCED_NCOL);
-        W::sync();
-        return rc;
-    }
-};
-
-template <class W, int CAP>
-struct RunSet<W, SET_CESIUM, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_CESIUM, CAP>& ws, double* row, int32_t*) {
-        stage_object<W, CAP>(in, ws.obj);
-        cesium_object<W, CAP>(ws.obj, ws.s);
-        store_row<W>(ws.s.out, row, CESIUM_NCOL);
-        W::sync();
-        return 0;
-    }
-};
-template <class W, int CAP>
-struct RunSet<W, SET_FOURIER, CAP> {
-    static LCFE_FN int run(const ObjIn& in, SetLds<SET_FOURIER, CAP>& ws, double* row, int32_t*) {
-        stage_object<W, CAP>(in, ws.obj);
-        fourier_object<W, CAP>(ws.obj, ws.s);
-        store_row<W>(ws.s.out, row, FOURIER_NCOL);
-        W::sync();
         return 0;
     }
 };

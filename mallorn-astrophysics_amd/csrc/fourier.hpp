@@ -124,4 +124,7 @@ LCFE_FN void fourier_object(const ObjLds<CAP>& L, FourierLds<CAP>& S) {
     }
 }
 
+template <class W, class G, int CAP>   // RunSet's hook (feature_sets.hpp); G: policy of one per-band pass or fit
+LCFE_FN int run_object(const ObjLds<CAP>& L, const ObjIn&, FourierLds<CAP>& S, int32_t*) { fourier_object<W, CAP>(L, S); return 0; }
+
 }  // namespace lcfe

@@ -85,11 +85,36 @@ constexpr int kStatW32List = 2 * kNumBins + 8;        // ... up to 512 rows, the
 constexpr int kBazinLongList = 2 * kNumBins + 9;      // light curves of more than 1024 rows with a band beyond the largest fit tier
 constexpr int kPowerlawLongList = 2 * kNumBins + 10;  // ... with more post-peak rows in a band than the largest fit tier
 constexpr int kResearchLongList = 2 * kNumBins + 11;  // light curves whose r band spans more days than the Mexican-hat grid in LDS
+static_assert(SetTraits<SET_RESEARCH>::overflow_list == kResearchLongList, "the research set's overflow list");
 constexpr int kGpSortedList = 2 * kNumBins + 12;      // + tier (0..5): the 2-D GP tier's light curves, longest first (gp_sort_kernel)
 struct Bins {
     int* lists;                        // [kNumLists][n_obj]: set tiers, GP tiers, statistics fallback
     int* counts;                       // [kNumLists]
     int64_t stride;                    // n_obj
+};
+
+// What every launcher of a set gets, built once per set by lcfe_extract_device: the batch and its bins, where the set's
+// columns and status words go, its stream, and its share of the workspace; the launchers are its members.
+struct SetLaunch {
+    const BatchView& B;
+    const Bins& bins;
+    int64_t max_len;
+    double* out;
+    int ld, col0;
+    int32_t* status;
+    int st_ld, st0;
+    hipStream_t stream;
+    int dev;
+    int* n_launch;
+    unsigned long long* tickets;
+    char* long_slabs;
+    // the five sets with launch sequences of their own (+ their extras), and every other set
+    int launch_stat(hipStream_t s1, hipStream_t s2) const;
+    int launch_bazin(void* ws, size_t ws_bytes, int64_t n_points) const;
+    int launch_powerlaw(void* ws, size_t ws_bytes, int64_t n_points) const;
+    int launch_gp(const hipStream_t* gs, int ngs, double* kscratch, size_t kscratch_bytes) const;
+    int launch_gp1d(double* kslab) const;
+    template <int SET> int launch_set() const;
 };
 
 __device__ __forceinline__ int set_bin_of(int64_t n) {
@@ -169,10 +194,9 @@ __device__ void nan_fill_bins(const Bins& bins, int g, int from, double* out, in
 // cheap streaming sets take 8 objects per ticket; the fits take one); the chunk's list entries and
 // CSR offsets are fetched by its first lanes in one go.  The launch of the last tier also writes the
 // NaN rows of the objects that are too long for it (bins >= nan_from).
-// minimum waves per SIMD the register allocation must leave room for: the bounded fits are long
-// dependent fp64 chains, so a second wave per SIMD matters more than keeping every value in a register
-// (only the 128-row tier: the larger tiers are limited to one wave per SIMD by their LDS footprint anyway)
-template <int SET, int CAP> struct set_waves { static constexpr int N = ((SET == SET_BAZIN || SET == SET_POWERLAW) && CAP <= 128) ? 2 : 1; };
+// minimum waves per SIMD the register allocation must leave room for (SetTraits::waves128; only the 128-row tier: the
+// larger tiers are limited to one wave per SIMD by their LDS footprint anyway)
+template <int SET, int CAP> struct set_waves { static constexpr int N = (CAP <= 128) ? SetTraits<SET>::waves128 : 1; };
 
 template <int SET, int CAP>
 __global__ __launch_bounds__(64, (set_waves<SET, CAP>::N)) void set_kernel(BatchView B, Bins bins, int bin, int nan_from, double* out,
@@ -181,8 +205,8 @@ __global__ __launch_bounds__(64, (set_waves<SET, CAP>::N)) void set_kernel(Batch
     __shared__ SetLds<SET, CAP> ws;
     __shared__ long long next_ticket;
     using W = WaveDev;
-    const int ncol = set_ncols(SET);
-    const int nst = set_nstatus(SET);
+    const int ncol = SetTraits<SET>::ncols;
+    const int nst = SetTraits<SET>::nstatus;
     const int count = bins.counts[bin];
     const int* list = bins.lists + (int64_t)bin * bins.stride;
     // a sparsely filled tier hands out smaller tickets, so that every wave gets several of them
@@ -213,11 +237,11 @@ __global__ __launch_bounds__(64, (set_waves<SET, CAP>::N)) void set_kernel(Batch
             ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, n, B.z ? B.z[i] : qnan()};
             LCFE_PT(5);
             const int rc = RunSet<W, SET, CAP>::run(in, ws, row, st);
-            if constexpr (SET == SET_RESEARCH) {
-                // r band longer than the Mexican-hat grid of this tier: the long-object tier takes the light curve
+            if constexpr (SetTraits<SET>::overflow_list >= 0) {
+                // (research: r band longer than the Mexican-hat grid of this tier) the long-object tier takes the light curve
                 if (rc == -100 && threadIdx.x == 0) {
-                    const int slot = atomicAdd(&bins.counts[kResearchLongList], 1);
-                    bins.lists[(int64_t)kResearchLongList * bins.stride + slot] = (int)i;
+                    const int slot = atomicAdd(&bins.counts[SetTraits<SET>::overflow_list], 1);
+                    bins.lists[(int64_t)SetTraits<SET>::overflow_list * bins.stride + slot] = (int)i;
                 }
             }
             (void)rc;
@@ -304,7 +328,7 @@ __global__ __launch_bounds__(64) void set_long_kernel(BatchView B, Bins bins, in
     using W = LongDev;
     __shared__ long long next_ticket;
     SetLds<SET, kLongCap>& ws = *reinterpret_cast<SetLds<SET, kLongCap>*>(slabs + (size_t)blockIdx.x * long_slab_bytes<SET>());
-    const int ncol = set_ncols(SET), nst = set_nstatus(SET);
+    const int ncol = SetTraits<SET>::ncols, nst = SetTraits<SET>::nstatus;
     const int c0 = (l0 >= 0) ? bins.counts[l0] : 0, c1 = (l1 >= 0) ? bins.counts[l1] : 0, c2 = (l2 >= 0) ? bins.counts[l2] : 0;
     for (;;) {
         if (threadIdx.x == 0) next_ticket = (long long)atomicAdd(ticket, 1ull);
@@ -529,7 +553,7 @@ constexpr int kFitTiers = 5;
 constexpr int kFitCaps[kFitTiers] = {16, 32, 64, 128, 256}; // rows of one band
 constexpr int kFitCountBase = 32;                           // counts[32 + t]: length of fit list t
 // (the ticket counters of the fit lists sit behind those of the numbered sets and the extension set: 8 per set, 13 sets;
-// the registered sets, bits 14 on, have theirs behind the bin counts -- set_ticket_base)
+// the registered sets, bits 14 on, have theirs behind the bin counts -- SetTraits::ticket_base)
 constexpr int kFitTicketBase = 112;                         // tickets[112 + t]
 static_assert(kFitTicketBase >= (SET_ADVANCED + 1) * 8, "fit tickets behind the sets' tickets");
 // tier of a band of m rows (m <= 256); narrow == 0 queues the bands of up to 16 rows on the 32-row list (LCFE_FIT_NARROW=0)
@@ -1117,10 +1141,8 @@ int launch_gp_tier(const BatchView& B, const Bins& bins, int bin, int nan_from, 
     return 0;
 }
 
-int launch_gp(const BatchView& B, const Bins& bins, int64_t max_len, double* out, int ld, int col0, int32_t* status,
-              int st_ld, int st0, const hipStream_t* gs, int ngs, int dev, double* kscratch,
-              size_t kscratch_bytes, int* n_launch, unsigned long long* tickets, char* long_slabs) {
-    hipStream_t stream = gs[0], stream2 = gs[(ngs > 1) ? 1 : 0];
+int SetLaunch::launch_gp(const hipStream_t* gs, int ngs, double* kscratch, size_t kscratch_bytes) const {
+    hipStream_t stream2 = gs[(ngs > 1) ? 1 : 0];
     // (A variant that keeps the matrix in the REGISTERS of the workgroup -- 2-D block-cyclic tiles,
     // register-tiled outer products -- was built and measured: slower on every tier, because hipcc
     // spends 412-512 registers per lane on the unrolled tile passes and spills at 1024 threads.)
@@ -1530,9 +1552,7 @@ __global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B,
 // object; bins 3..5 (160..767 rows) with the 160-row matrix, a band of 160..767 valid points with the 768-row one in
 // global scratch; bin 6 (more than 767 rows) in the long-object tier when the workspace holds its slabs (long_slab),
 // NaN and status -100 otherwise.
-int launch_gp1d(const BatchView& B, const Bins& bins, int64_t max_len, double* out, int ld, int col0, int32_t* status,
-                int st_ld, int st0, hipStream_t stream, int dev, int* n_launch, unsigned long long* tickets, double* kslab,
-                char* long_slab) {
+int SetLaunch::launch_gp1d(double* kslab) const {
     const int caps[6] = {63, 111, 159, kGpSmallNP - 1, kGpMidNP - 1, kGpGlobalNP - 1};
     int last = 0;
     while (last < 5 && caps[last] < max_len) ++last;
@@ -1552,23 +1572,20 @@ int launch_gp1d(const BatchView& B, const Bins& bins, int64_t max_len, double* o
     // light curves of more than 767 rows (bin 6): they overwrite the NaN rows and status -100 of the tier-5 launch, which
     // ran before them on this stream.  Last on the stream, so that the short tiers do not wait for 8 workgroups that may
     // take seconds per light curve.
-    if (long_slab && max_len > kGpGlobalNP - 1) {
+    if (long_slabs && max_len > SetTraits<SET_GP1D>::long_above) {
         hipLaunchKernelGGL(gp1d_long_kernel, dim3(kGp1dLongTierGrid), dim3(kGp1dThreads), 0, stream, B, bins, out, ld, col0, status,
-                           st_ld, st0, long_slab, tickets + SET_GP1D * 8 + 7);
+                           st_ld, st0, long_slabs, tickets + SET_GP1D * 8 + 7);
         HIP_TRY(hipGetLastError());
         ++*n_launch;
     }
     return 0;
 }
 
-// first of the 8 ticket counters of a set: tickets[8 s] up to the extension set; the registered sets (bits 14 on) continue
-// at tickets[256], behind the bin counts, because tickets[112..128) belong to the fit lists
+// ticket counters of the registered sets (SetTraits::ticket_base): tickets[256] on, behind the bin counts
 constexpr int kRegTicketBase = 256, kRegTicketSets = 4;
-constexpr int set_ticket_base(int set) { return (set <= SET_ADVANCED) ? set * 8 : kRegTicketBase + (set - SET_CESIUM) * 8; }
-static_assert(NUM_ALL_SETS - SET_CESIUM <= kRegTicketSets, "ticket counters of the registered sets");
+static_assert(SetTraits<SET_CESIUM>::ticket_base == kRegTicketBase && NUM_ALL_SETS - SET_CESIUM <= kRegTicketSets,
+              "ticket counters of the registered sets");
 
-const int kTiers[] = {128, 256, 512, 1024, 2048};
-constexpr int kMaxPoints = 2048;
 
 int g_num_cu[16] = {0};
 std::mutex g_num_cu_mutex;
@@ -1593,7 +1610,7 @@ int launch_tier(const BatchView& B, const Bins& bins, int bin, int nan_from, dou
     if (per_cu < 1) per_cu = 1;
     int64_t grid = (int64_t)num_cus(dev) * per_cu;
     if (grid > max_grid) grid = max_grid;
-    const int chunk = (SET == SET_BAZIN || SET == SET_POWERLAW) ? 1 : 8;
+    const int chunk = SetTraits<SET>::chunk;
     if (grid * chunk > B.n_obj) grid = (B.n_obj + chunk - 1) / chunk;
     if (grid < 1) return 0;
     hipLaunchKernelGGL((set_kernel<SET, CAP>), dim3((unsigned)grid), dim3(64), 0, stream, B, bins, bin, nan_from,
@@ -1602,22 +1619,16 @@ int launch_tier(const BatchView& B, const Bins& bins, int bin, int nan_from, dou
     return 0;
 }
 
-// largest LDS tier a set's working memory fits in (160 KiB per workgroup)
 template <int SET>
-constexpr int max_tier() {
-    return (SET == SET_BAZIN || SET == SET_POWERLAW || SET == SET_RESEARCH) ? 3 : 4;
-}
-
-template <int SET>
-int launch_set(const BatchView& B, const Bins& bins, int64_t max_len, double* out, int ld, int col0, int32_t* status,
-               int st_ld, int st0, hipStream_t stream, int dev, int* n_launch, unsigned long long* tickets, char* long_slabs) {
+int SetLaunch::launch_set() const {
+    using T = SetTraits<SET>;
     // tiers needed: every tier whose window (prev_cap, cap] can contain an object, i.e. up to the
     // first cap >= max_len; the last launched tier also NaN-fills the bins of longer objects.
     int last = 0;
-    while (last < max_tier<SET>() && kTiers[last] < max_len) ++last;
+    while (last < T::max_tier && kTiers[last] < max_len) ++last;
     for (int ti = 0; ti <= last; ++ti) {
         const int nan_from = (ti == last) ? ti + 1 : kNumBins;
-        unsigned long long* tk = tickets + set_ticket_base(SET) + ti;
+        unsigned long long* tk = tickets + T::ticket_base + ti;
         int rc = 0;
         switch (ti) {
             case 0: rc = launch_tier<SET, 128>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk); break;
@@ -1625,18 +1636,18 @@ int launch_set(const BatchView& B, const Bins& bins, int64_t max_len, double* ou
             case 2: rc = launch_tier<SET, 512>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk); break;
             case 3: rc = launch_tier<SET, 1024>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk); break;
             case 4:
-                if constexpr (max_tier<SET>() >= 4)
+                if constexpr (T::max_tier >= 4)
                     rc = launch_tier<SET, 2048>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk);
                 break;
         }
         if (rc) return rc;
         ++*n_launch;
     }
-    // the long-object tier: bin 6 (more than 2048 rows); the research set's LDS tiers end at 1024 rows (bin 4 too) and at
-    // 4096 days of r band (its overflow list)
-    if (long_slabs && (max_len > kTiers[max_tier<SET>()] || SET == SET_RESEARCH)) {
-        const int rc = launch_long<SET>(B, bins, 6, (SET == SET_RESEARCH) ? 4 : -1, (SET == SET_RESEARCH) ? kResearchLongList : -1, out, ld, col0,
-                                        status, st_ld, st0, stream, tickets + set_ticket_base(SET) + 7, long_slabs);
+    // the long-object tier: bin 6 (more than 2048 rows), bin 4 too where the set's LDS tiers end at 1024 rows, and the set's
+    // overflow list (research: more than 4096 days of r band)
+    if (long_slabs && (max_len > T::long_above || T::overflow_list >= 0)) {
+        const int rc = launch_long<SET>(B, bins, 6, (T::max_tier < 4) ? 4 : -1, T::overflow_list, out, ld, col0,
+                                        status, st_ld, st0, stream, tickets + T::ticket_base + 7, long_slabs);
         if (rc) return rc;
         ++*n_launch;
     }
@@ -1697,9 +1708,7 @@ int launch_bazin_fits(const BatchView& B, const Bins& bins, const FitWs& F, int 
 
 // Bazin: partition pass per object tier, the fit kernel per band-length tier (longest first), the object-level
 // kernel for objects with a band beyond the largest fit tier, then the cross-band columns.
-int launch_bazin(const BatchView& B, const Bins& bins, int64_t max_len, double* out, int ld, int col0, int32_t* status, int st_ld,
-                 int st0, hipStream_t stream, int dev, int* n_launch, unsigned long long* tickets, void* ws, size_t ws_bytes,
-                 int64_t n_points, char* long_slabs) {
+int SetLaunch::launch_bazin(void* ws, size_t ws_bytes, int64_t n_points) const {
     if (!ws || ws_bytes < bazin_ws_bytes(B.n_obj, n_points))
         return fail_msg("lcfe_extract_device: workspace too small for the Bazin fit lists");
     const size_t np = (size_t)(n_points > 0 ? n_points : 1), no = (size_t)B.n_obj;
@@ -1745,7 +1754,7 @@ int launch_bazin(const BatchView& B, const Bins& bins, int64_t max_len, double* 
     HIP_TRY(hipGetLastError());
     ++*n_launch;
     // the long-object tier: more than 2048 rows (bin 6), or more than 1024 rows with a band beyond the fit tiers (all 52 columns)
-    if (long_slabs && max_len > 1024) {
+    if (long_slabs && max_len > SetTraits<SET_BAZIN>::long_above) {
         rc = launch_long<SET_BAZIN>(B, bins, 6, kBazinLongList, -1, out, ld, col0, status, st_ld, st0, stream, tk + 7, long_slabs);
         if (rc) return rc;
         ++*n_launch;
@@ -1791,9 +1800,7 @@ int launch_powerlaw_fits(const BatchView& B, const Bins& bins, const PlWs& F, in
     return 0;
 }
 
-int launch_powerlaw(const BatchView& B, const Bins& bins, int64_t max_len, double* out, int ld, int col0, int32_t* status, int st_ld,
-                    int st0, hipStream_t stream, int dev, int* n_launch, unsigned long long* tickets, void* ws, size_t ws_bytes,
-                    int64_t n_points, char* long_slabs) {
+int SetLaunch::launch_powerlaw(void* ws, size_t ws_bytes, int64_t n_points) const {
     if (!ws || ws_bytes < powerlaw_ws_bytes(B.n_obj, n_points))
         return fail_msg("lcfe_extract_device: workspace too small for the decline-fit lists");
     const size_t np = (size_t)(n_points > 0 ? n_points : 1), no = (size_t)B.n_obj;
@@ -1836,7 +1843,7 @@ int launch_powerlaw(const BatchView& B, const Bins& bins, int64_t max_len, doubl
 #undef PL_TIER
     if (rc) return rc;
     *n_launch += 8;
-    if (long_slabs && max_len > 1024) {
+    if (long_slabs && max_len > SetTraits<SET_POWERLAW>::long_above) {
         rc = launch_long<SET_POWERLAW>(B, bins, 6, kPowerlawLongList, -1, out, ld, col0, status, st_ld, st0, stream, tk + 7, long_slabs);
         if (rc) return rc;
         ++*n_launch;
@@ -1882,8 +1889,7 @@ static bool stat_lanes_enabled() {
 
 // Statistics: lean kernels for the tiers up to 512 rows, the general kernel for the longer tiers,
 // for the lean kernels' fallback list and for the NaN rows of over-long objects.
-int launch_stat(const BatchView& B, const Bins& bins, int64_t max_len, double* out, int ld, int col0,
-                hipStream_t stream, int dev, int* n_launch, unsigned long long* tickets, hipStream_t s1, hipStream_t s2, char* long_slabs) {
+int SetLaunch::launch_stat(hipStream_t s1, hipStream_t s2) const {
     int last = 0;
     while (last < 4 && kTiers[last] < max_len) ++last;
     unsigned long long* tk = tickets + SET_STAT * 8;
@@ -1960,7 +1966,7 @@ int launch_stat(const BatchView& B, const Bins& bins, int64_t max_len, double* o
     else rc = launch_tier<SET_STAT, 512>(B, bins, kStatFallbackList, nan_from, out, ld, col0, nullptr, 0, 0, stream, dev, tk + 5, fb_grid);
     if (rc) return rc;
     ++*n_launch;
-    if (long_slabs && max_len > kMaxPoints) {
+    if (long_slabs && max_len > SetTraits<SET_STAT>::long_above) {
         rc = launch_long<SET_STAT>(B, bins, 6, -1, -1, out, ld, col0, nullptr, 0, 0, stream, tk + 7, long_slabs);
         if (rc) return rc;
         ++*n_launch;
@@ -1971,10 +1977,11 @@ int launch_stat(const BatchView& B, const Bins& bins, int64_t max_len, double* o
 #include "colnames.inc"
 
 bool set_implemented(int set) { return set_known(set); }
-
-// names of the sets by mask bit (lcfe_set_info); the hole at bit 13 has none
-const char* const kSetNames[NUM_ALL_SETS] = {"stat", "bazin", "powerlaw", "tde", "color", "shape", "physics", "gp2d", "gp1d", "research",
-                                             "ecolor", "decline", "advanced", nullptr, "cesium", "fourier"};
+// the table's column counts are those of the generated column names (the hole at bit 13 has none)
+static_assert(sizeof kColCount / sizeof kColCount[0] == NUM_ALL_SETS && kColCount[SET_UNASSIGNED] == 0, "colnames.inc: one table per mask bit");
+#define LCFE_CHECK_COLS(ID, ...) static_assert(SetTraits<ID>::ncols == kColCount[ID], "feature_sets.hpp and colnames.inc disagree on the columns of " #ID);
+LCFE_SET_TABLE(LCFE_CHECK_COLS)
+#undef LCFE_CHECK_COLS
 
 // profile of every set of the last call this thread made with prof != NULL (lcfe_last_set_profile; lcfe_last_ext_profile
 // reads the extension sets' entries)
@@ -2089,7 +2096,7 @@ int lcfe_set_info(int k, int* bit, const char** name, int* ncols, int* nstatus) 
     for (int s = 0; s < NUM_ALL_SETS; ++s) {
         if (!set_implemented(s) || k-- != 0) continue;
         if (bit) *bit = s;
-        if (name) *name = kSetNames[s];
+        if (name) *name = set_name(s);
         if (ncols) *ncols = set_ncols(s);
         if (nstatus) *nstatus = set_nstatus(s);
         return 0;
@@ -2158,25 +2165,15 @@ size_t lcfe_workspace_bytes(int mask, int64_t n_obj, int64_t n_points) {
 
 // slabs of the long-object tier of one set (0: the set needs none for light curves of up to max_len rows)
 static size_t long_bytes_of(int set, int64_t max_len) {
-    switch (set) {
-        case SET_STAT: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_STAT>() : 0;
-        case SET_BAZIN: return (max_len > 1024) ? kLongGrid * long_slab_bytes<SET_BAZIN>() : 0;
-        case SET_POWERLAW: return (max_len > 1024) ? kLongGrid * long_slab_bytes<SET_POWERLAW>() : 0;
-        case SET_TDE: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_TDE>() : 0;
-        case SET_COLOR: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_COLOR>() : 0;
-        case SET_SHAPE: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_SHAPE>() : 0;
-        case SET_PHYSICS: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_PHYSICS>() : 0;
-        case SET_GP2D: return (max_len > kGpGlobalNP - 1) ? kGpLongBytes : 0;
-        case SET_GP1D: return (max_len > kGpGlobalNP - 1) ? kGp1dLongTierBytes : 0;
-        case SET_RESEARCH: return kLongGrid * long_slab_bytes<SET_RESEARCH>();     // (an r band of more than 4096 days can sit in a short light curve)
-        case SET_ECOLOR: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_ECOLOR>() : 0;
-        case SET_DECLINE: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_DECLINE>() : 0;
-        case SET_ADVANCED: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_ADVANCED>() : 0;
-        case SET_CESIUM: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_CESIUM>() : 0;
-        case SET_FOURIER: return (max_len > kMaxPoints) ? kLongGrid * long_slab_bytes<SET_FOURIER>() : 0;
-    }
-    return 0;
+    return for_set(set, [&](auto tag) -> size_t {
+        using T = SetTraits<tag()>;
+        if (max_len <= T::long_above && T::overflow_list < 0) return 0;   // (an overflow list can fill from short light curves)
+        if constexpr (tag() == SET_GP2D) return kGpLongBytes;
+        else if constexpr (tag() == SET_GP1D) return kGp1dLongTierBytes;
+        else return kLongGrid * long_slab_bytes<tag()>();
+    });
 }
+static_assert(SetTraits<SET_GP2D>::long_above == kGpGlobalNP - 1 && SetTraits<SET_GP1D>::long_above == kGpGlobalNP - 1, "last GP tier");
 
 size_t lcfe_workspace_bytes_for(int mask, int64_t n_obj, int64_t n_points, int64_t max_len) {
     size_t b = lcfe_workspace_bytes(mask, n_obj, n_points);
@@ -2257,17 +2254,6 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
     static const bool serial = [] { const char* e = getenv("LCFE_SERIAL"); return e && e[0] == '1'; }();
     hipStream_t side[kSideStreams];
     const bool fork = !serial && side_streams(dev, side) == 0;
-    // stream of each set: GP (the longest) stays on the caller's stream
-    auto stream_of = [&](int s) -> hipStream_t {
-        if (!fork) return stream;
-        switch (s) {
-            case SET_BAZIN: return side[0];
-            case SET_POWERLAW: return side[1];
-            case SET_TDE: case SET_COLOR: case SET_SHAPE: case SET_PHYSICS: case SET_GP1D: case SET_RESEARCH:
-            case SET_ECOLOR: case SET_DECLINE: case SET_ADVANCED: case SET_CESIUM: case SET_FOURIER: return side[2];
-            default: return stream;
-        }
-    };
     // timing events (prof only): created once per host thread and device, reused by later calls -- a call with
     // `prof` drains the stream before it returns, so the events of the previous call are always complete
     struct Events {
@@ -2301,34 +2287,26 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
                                stream, d_offsets, n_obj, lists, counts);
             HIP_TRY(hipGetLastError());
         }
-        hipStream_t q = stream_of(s);
+        // stream of the set (SetTraits::stream): the 2-D GP (the longest) and the statistics stay on the caller's stream
+        const int side_k = for_set(s, [](auto tag) { return SetTraits<tag()>::stream; }, int(STREAM_CALLER));
+        hipStream_t q = (fork && side_k >= 0) ? side[side_k] : stream;
         if (fork && s != SET_STAT && !forked) {
             HIP_TRY(hipEventCreateWithFlags(&forked, hipEventDisableTiming));
             HIP_TRY(hipEventRecord(forked, stream));
         }
         if (q != stream) {
-            const int k = (q == side[0]) ? 0 : (q == side[1]) ? 1 : 2;
-            if (!side_used[k]) { HIP_TRY(hipStreamWaitEvent(q, forked, 0)); side_used[k] = true; }
+            if (!side_used[side_k]) { HIP_TRY(hipStreamWaitEvent(q, forked, 0)); side_used[side_k] = true; }
         }
         if (prof && ne != 0) HIP_TRY(hipEventRecord(ev0[s], q));
-        int nl = 0, rc = 0;
-        switch (s) {
-            case SET_STAT: rc = launch_stat(B, bins, max_len, d_out, ld, col0, q, dev, &nl, tickets, fork ? side[0] : q, fork ? side[1] : q, long_slab[s]); break;
-            case SET_BAZIN: rc = launch_bazin(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, bazin_ws, bazin_bytes, n_points, long_slab[s]); break;
-            case SET_POWERLAW: rc = launch_powerlaw(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, pl_ws, pl_bytes, n_points, long_slab[s]); break;
-            case SET_TDE: rc = launch_set<SET_TDE>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
-            case SET_COLOR: rc = launch_set<SET_COLOR>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
-            case SET_SHAPE: rc = launch_set<SET_SHAPE>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
-            case SET_PHYSICS: rc = launch_set<SET_PHYSICS>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
-            case SET_RESEARCH: rc = launch_set<SET_RESEARCH>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
-            case SET_ECOLOR: rc = launch_set<SET_ECOLOR>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
-            case SET_DECLINE: rc = launch_set<SET_DECLINE>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
-            case SET_ADVANCED: rc = launch_set<SET_ADVANCED>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
-            case SET_CESIUM: rc = launch_set<SET_CESIUM>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
-            case SET_FOURIER: rc = launch_set<SET_FOURIER>(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]); break;
-            case SET_GP1D: rc = launch_gp1d(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, gp1d_slab, long_slab[s]); break;
-            case SET_GP2D:
-            {
+        int nl = 0;
+        const SetLaunch A{B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]};
+        const int rc = for_set(s, [&](auto tag) -> int {
+            constexpr int SET = tag();
+            if constexpr (SET == SET_STAT) return A.launch_stat(fork ? side[0] : q, fork ? side[1] : q);
+            else if constexpr (SET == SET_BAZIN) return A.launch_bazin(bazin_ws, bazin_bytes, n_points);
+            else if constexpr (SET == SET_POWERLAW) return A.launch_powerlaw(pl_ws, pl_bytes, n_points);
+            else if constexpr (SET == SET_GP1D) return A.launch_gp1d(gp1d_slab);
+            else if constexpr (SET == SET_GP2D) {
                 // the GP tiers, longest first, round-robin over the caller's stream and side streams 2.. (LCFE_GP_STREAMS, default
                 // 2: more streams start more tiers at once)
                 static const int want = [] { const char* e = getenv("LCFE_GP_STREAMS"); const int k = e ? atoi(e) : 2; return (k < 1) ? 1 : ((k > 4) ? 4 : k); }();
@@ -2341,8 +2319,7 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
                     }
                     ngs = want;
                 }
-                rc = launch_gp(B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, gs, ngs, dev, gp_scratch,
-                               gp_scratch_bytes, &nl, tickets, long_slab[s]);
+                int rc = A.launch_gp(gs, ngs, gp_scratch, gp_scratch_bytes);
                 // the set's stop event (prof) is recorded on q: make q wait for the tiers on the other streams
                 for (int k = 1; k < ngs && !rc; ++k) {
                     hipEvent_t half;
@@ -2351,9 +2328,9 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
                     HIP_TRY(hipStreamWaitEvent(q, half, 0));
                     (void)hipEventDestroy(half);
                 }
-                break;
-            }
-        }
+                return rc;
+            } else return A.template launch_set<SET>();
+        });
         if (rc) return rc;
         if (prof) {
             HIP_TRY(hipEventRecord(ev1[s], q));

@@ -252,4 +252,7 @@ LCFE_FN void physics_object(const ObjLds<CAP>& L, double z_in, PhysicsLds<CAP>& 
     W::sync();
 }
 
+template <class W, class G, int CAP>   // RunSet's hook (feature_sets.hpp); G: policy of one per-band pass or fit
+LCFE_FN int run_object(const ObjLds<CAP>& L, const ObjIn& in, PhysicsLds<CAP>& S, int32_t*) { physics_object<W, CAP>(L, in.z, S); return 0; }
+
 }  // namespace lcfe

@@ -466,4 +466,11 @@ LCFE_FN int research_object(const ObjLds<CAP>& L, double z, ResearchLds<CAP>& S)
     return fits_grid ? 0 : -100;
 }
 
+template <class W, class G, int CAP>   // RunSet's hook (feature_sets.hpp); G: policy of one per-band pass or fit
+LCFE_FN int run_object(const ObjLds<CAP>& L, const ObjIn& in, ResearchLds<CAP>& S, int32_t* st) {
+    const int rc = research_object<W, CAP>(L, in.z, S);
+    if (st && W::lane() == 0) st[0] = rc;
+    return rc;
+}
+
 }  // namespace lcfe

@@ -210,4 +210,7 @@ LCFE_FN void shape_object(const ObjLds<CAP>& L, ShapeLds<CAP>& S) {
     W::sync();
 }
 
+template <class W, class G, int CAP>   // RunSet's hook (feature_sets.hpp); G: policy of one per-band pass or fit
+LCFE_FN int run_object(const ObjLds<CAP>& L, const ObjIn&, ShapeLds<CAP>& S, int32_t*) { shape_object<W, G, CAP>(L, S); return 0; }
+
 }  // namespace lcfe

@@ -327,4 +327,7 @@ LCFE_FN void tde_object(const ObjLds<CAP>& L, TdeLds<CAP>& S) {
     W::sync();
 }
 
+template <class W, class G, int CAP>   // RunSet's hook (feature_sets.hpp); G: policy of one per-band pass or fit
+LCFE_FN int run_object(const ObjLds<CAP>& L, const ObjIn&, TdeLds<CAP>& S, int32_t*) { tde_object<W, CAP>(L, S); return 0; }
+
 }  // namespace lcfe

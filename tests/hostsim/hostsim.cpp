@@ -7,7 +7,7 @@
 #include <memory>
 #include <vector>
 
-#include "../../mallorn-astrophysics_amd/csrc/feature_sets.hpp"
+#include "run_all.hpp"
 
 using namespace lcfe;
 
@@ -16,29 +16,6 @@ using namespace lcfe;
 #endif
 
 extern "C" int hostsim_max_points() { return HOSTSIM_CAP; }
-
-template <int SET>
-static void run_all(int64_t n_obj, const int64_t* offsets, const double* t, const double* flux,
-                    const double* err, const uint8_t* band, const double* z, double* out,
-                    int32_t* status) {
-    using W = WaveHost;
-    auto ws = std::make_unique<SetLds<SET, HOSTSIM_CAP>>();
-    const int ncol = set_ncols(SET);
-    const int nst = set_nstatus(SET);
-    for (int64_t i = 0; i < n_obj; ++i) {
-        const int64_t s = offsets[i];
-        const int n = (int)(offsets[i + 1] - s);
-        double* row = out + i * ncol;
-        int32_t* st = (status && nst) ? status + i * nst : nullptr;
-        if (n > HOSTSIM_CAP) {
-            fill_row_nan<W>(row, ncol);
-            for (int k = 0; k < nst; ++k) if (st) st[k] = -100;
-            continue;
-        }
-        ObjIn in{t + s, flux + s, err + s, band + s, n, z ? z[i] : qnan()};
-        RunSet<W, SET, HOSTSIM_CAP>::run(in, *ws, row, st);
-    }
-}
 
 // the GP kernel has its own working set (Gram matrix) and reads the CSR slice directly; like the
 // device it uses the 8-wide sweep for short light curves and the 16-wide one for long ones
@@ -72,18 +49,15 @@ static void run_gp(int64_t n_obj, const int64_t* offsets, const double* t, const
 extern "C" int hostsim_extract(int set, int64_t n_obj, const int64_t* offsets, const double* t,
                                const double* flux, const double* err, const uint8_t* band,
                                const double* z, double* out, int32_t* status) {
-    switch (set) {
-        case SET_STAT: run_all<SET_STAT>(n_obj, offsets, t, flux, err, band, z, out, status); return 0;
-        case SET_BAZIN: run_all<SET_BAZIN>(n_obj, offsets, t, flux, err, band, z, out, status); return 0;
-        case SET_POWERLAW: run_all<SET_POWERLAW>(n_obj, offsets, t, flux, err, band, z, out, status); return 0;
-        case SET_TDE: run_all<SET_TDE>(n_obj, offsets, t, flux, err, band, z, out, status); return 0;
-        case SET_COLOR: run_all<SET_COLOR>(n_obj, offsets, t, flux, err, band, z, out, status); return 0;
-        case SET_SHAPE: run_all<SET_SHAPE>(n_obj, offsets, t, flux, err, band, z, out, status); return 0;
-        case SET_PHYSICS: run_all<SET_PHYSICS>(n_obj, offsets, t, flux, err, band, z, out, status); return 0;
-        case SET_RESEARCH: run_all<SET_RESEARCH>(n_obj, offsets, t, flux, err, band, z, out, status); return 0;
-        case SET_GP2D: run_gp(n_obj, offsets, t, flux, err, band, out, status); return 0;
-        default: return 1;
-    }
+    if (set == SET_GP2D) { run_gp(n_obj, offsets, t, flux, err, band, out, status); return 0; }
+    // the per-object sets up to `research` (the later ones have libraries of their own)
+    return for_set(set, [&](auto s) {
+        if constexpr (s() <= SET_RESEARCH && SetTraits<s()>::per_object) {
+            run_all<s(), HOSTSIM_CAP>(n_obj, offsets, t, flux, err, band, z, out, status);
+            return 0;
+        }
+        return 1;
+    }, 1);
 }
 
 // ---- per-band 1-D GP (csrc/gp1d.hpp): the four bands g, r, i, z of every object, one after the other

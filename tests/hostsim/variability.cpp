@@ -3,10 +3,7 @@
 // through RunSet on the one-lane WaveHost policy, with the object's working set SetLds<SET, VARIABILITY_CAP> in heap
 // memory, and the log-normal-CDF of cesium.hpp on its own.  Light curves of more than VARIABILITY_CAP rows get the NaN row,
 // as beyond the device's last tier.
-#include <cstdint>
-#include <memory>
-
-#include "../../mallorn-astrophysics_amd/csrc/feature_sets.hpp"
+#include "run_all.hpp"
 
 using namespace lcfe;
 
@@ -16,33 +13,16 @@ using namespace lcfe;
 
 extern "C" int variability_cap() { return VARIABILITY_CAP; }
 
-template <int SET>
-static void run_all(int64_t n_obj, const int64_t* offsets, const double* t, const double* flux, const double* err,
-                    const uint8_t* band, double* out) {
-    using W = WaveHost;
-    auto ws = std::make_unique<SetLds<SET, VARIABILITY_CAP>>();
-    const int ncol = set_ncols(SET);
-    for (int64_t i = 0; i < n_obj; ++i) {
-        const int64_t s = offsets[i];
-        const int n = (int)(offsets[i + 1] - s);
-        double* row = out + i * ncol;
-        if (n > VARIABILITY_CAP) {
-            fill_row_nan<W>(row, ncol);
-            continue;
-        }
-        ObjIn in{t + s, flux + s, err + s, band + s, n, qnan()};
-        RunSet<W, SET, VARIABILITY_CAP>::run(in, *ws, row, nullptr);
-    }
-}
-
 // set: 14 = cesium, 15 = fourier; returns 1 for any other set
 extern "C" int variability_extract(int set, int64_t n_obj, const int64_t* offsets, const double* t, const double* flux,
                                    const double* err, const uint8_t* band, double* out) {
-    switch (set) {
-        case SET_CESIUM: run_all<SET_CESIUM>(n_obj, offsets, t, flux, err, band, out); return 0;
-        case SET_FOURIER: run_all<SET_FOURIER>(n_obj, offsets, t, flux, err, band, out); return 0;
-    }
-    return 1;
+    return for_set(set, [&](auto s) {
+        if constexpr (s() == SET_CESIUM || s() == SET_FOURIER) {
+            run_all<s(), VARIABILITY_CAP>(n_obj, offsets, t, flux, err, band, nullptr, out, nullptr);
+            return 0;
+        }
+        return 1;
+    }, 1);
 }
 
 // log of the standard normal CDF at x[0..n) and the scaled complementary error function at y[0..n) (y >= 1 / sqrt 2)

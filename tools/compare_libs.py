@@ -1,33 +1,53 @@
-"""Debug helper: run one feature set with two builds of liblcfe.so and compare the outputs bit for bit.
-usage: compare_libs.py SET N_OBJ SEED LIB_A LIB_B"""
+"""Debug helper: run feature sets with two builds of liblcfe.so and compare outputs and status words bit for bit.
+usage: compare_libs.py SETS N_OBJ SEED LIB_A LIB_B [ROWS]
+SETS: one set or a comma-separated list run in ONE call ("all": every set of the registry).  ROWS: a comma-separated
+list of row counts; the batch is then one hand-made light curve per count (synth.from_objects, as the tier tests build
+theirs, seeded with SEED) instead of synth.make_lightcurves(N_OBJ, SEED)."""
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if len(sys.argv) == 6:
-    name, n, seed, a, b = sys.argv[1:]
+if sys.argv[1] != "--child":      # (--child SETS N_OBJ SEED OUT.npz [ROWS]: one library, LCFE_LIB_PATH, run by the parent mode)
+    name, n, seed, a, b = sys.argv[1:6]
     outs = []
-    for lib in (a, b):
-        path = f"/tmp/cmp_{os.path.basename(lib)}.npy"
-        env = dict(os.environ, LCFE_LIB_PATH=os.path.abspath(lib))
-        subprocess.run([sys.executable, __file__, name, n, seed, path], env=env, check=True)
-        outs.append(np.load(path))
-    x, y = outs
+    with tempfile.TemporaryDirectory() as tmp:
+        for k, lib in enumerate((a, b)):
+            path = os.path.join(tmp, f"cmp_{k}.npz")
+            env = dict(os.environ, LCFE_LIB_PATH=os.path.abspath(lib))
+            subprocess.run([sys.executable, __file__, "--child", name, n, seed, path] + sys.argv[6:], env=env, check=True)
+            with np.load(path) as z:
+                outs.append((z["out"], z["status"]))
+    (x, sx), (y, sy) = outs
     same = (x == y) | (np.isnan(x) & np.isnan(y))
-    print("identical:", bool(same.all()), "differing entries:", int((~same).sum()), "of", same.size)
+    st_same = sx == sy
+    print("identical:", bool(same.all() and st_same.all()), "differing entries:", int((~same).sum()), "of", same.size,
+          "differing status words:", int((~st_same).sum()), "of", st_same.size)
     if not same.all():
         with np.errstate(all="ignore"):
             rel = np.abs(x - y) / np.maximum(np.abs(y), 1e-300)
         rel[same] = 0
         print("max rel diff", np.nanmax(rel), "objects differing", int((~same).any(1).sum()))
-    sys.exit(0 if same.all() else 1)
+    sys.exit(0 if same.all() and st_same.all() else 1)
 else:
     sys.path.insert(0, ROOT)
     from mallorn_astrophysics_amd import synth
+    from mallorn_astrophysics_amd.columns import SET_BITS
     from mallorn_astrophysics_amd.engine import extract_csr
-    name, n, seed, path = sys.argv[1:]
-    lc = synth.make_lightcurves(int(n), seed=int(seed))
-    np.save(path, extract_csr(name, lc, z=lc["z"]))
+    name, n, seed, path = sys.argv[2:6]
+    sets = sorted(SET_BITS, key=SET_BITS.get) if name == "all" else name.split(",")
+    if len(sys.argv) > 6:
+        rng = np.random.default_rng(int(seed))
+        objs = []
+        for rows in (int(r) for r in sys.argv[6].split(",")):
+            t = np.sort(59000 + rng.uniform(0, 800, rows))
+            f = 30 * np.exp(-0.5 * ((t - 59300) / 40) ** 2) + rng.normal(0, 1, rows)
+            objs.append((t, f, np.full(rows, 1.0), rng.choice(6, rows)))
+        lc = synth.from_objects(objs)
+    else:
+        lc = synth.make_lightcurves(int(n), seed=int(seed))
+    out, status = extract_csr(sets if len(sets) > 1 else sets[0], lc, z=lc["z"], return_status=True)
+    np.savez(path, out=out, status=status if status is not None else np.zeros((out.shape[0], 0), np.int32))
