@@ -97,6 +97,20 @@ inline R for_set(int set, F&& f, R unknown = {}) {
     }
     return unknown;
 }
+// the same for a run-time LDS tier: f(IntTag<rows of tier ti>{})
+template <int N> using IntTag = std::integral_constant<int, N>;
+template <class F, class R = std::invoke_result_t<F&, IntTag<128>>>
+inline R for_tier(int ti, F&& f) {
+    switch (ti) {
+        case 0: return f(IntTag<128>{});
+        case 1: return f(IntTag<256>{});
+        case 2: return f(IntTag<512>{});
+        case 3: return f(IntTag<1024>{});
+        case 4: return f(IntTag<2048>{});
+    }
+    return R{};
+}
+static_assert(kTiers[0] == 128 && kTiers[1] == 256 && kTiers[2] == 512 && kTiers[3] == 1024 && kTiers[4] == 2048, "for_tier");
 inline bool set_known(int set) { return for_set(set, [](auto) { return true; }); }
 inline int set_ncols(int set) { return for_set(set, [](auto s) { return SetTraits<s()>::ncols; }); }
 inline int set_nstatus(int set) { return for_set(set, [](auto s) { return SetTraits<s()>::nstatus; }); }

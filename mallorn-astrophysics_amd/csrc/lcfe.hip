@@ -17,6 +17,7 @@
 
 #include "../../include/lcfe.h"
 #include "feature_sets.hpp"
+#include "workspace.hpp"
 #include "stat_lean.hpp"
 #include "stat_lanes.hpp"
 #include "stat_lanes16.hpp"
@@ -59,6 +60,52 @@ int fail_msg(const std::string& m) {
         if (e_ != hipSuccess) return fail(#expr, e_, __FILE__, __LINE__); \
     } while (0)
 
+int g_num_cu[16] = {0};
+std::mutex g_num_cu_mutex;
+
+int num_cus(int dev) {
+    if (dev < 0 || dev >= 16) return 256;
+    std::lock_guard<std::mutex> lock(g_num_cu_mutex);
+    if (!g_num_cu[dev]) {
+        hipDeviceProp_t p;
+        if (hipGetDeviceProperties(&p, dev) == hipSuccess) g_num_cu[dev] = p.multiProcessorCount;
+        else g_num_cu[dev] = 256;
+    }
+    return g_num_cu[dev];
+}
+
+// The streams dst[0..n) wait for what has been enqueued on src so far.  The event is short-lived: one that was recorded is
+// released by the runtime once the recorded work has completed, so destroying it right after the waits were enqueued is safe.
+int stream_wait(const hipStream_t* dst, int n, hipStream_t src) {
+    hipEvent_t e;
+    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    hipError_t err = hipEventRecord(e, src);
+    for (int k = 0; k < n && err == hipSuccess; ++k) err = hipStreamWaitEvent(dst[k], e, 0);
+    (void)hipEventDestroy(e);
+    return (err == hipSuccess) ? 0 : fail("stream_wait", err, __FILE__, __LINE__);
+}
+int stream_wait(hipStream_t dst, hipStream_t src) { return stream_wait(&dst, 1, src); }
+
+// One persistent launch: as many workgroups as the occupancy query says the chip holds (grid_for: caps, clamp to the
+// tickets of work, nothing to launch for no work), handed `args`.  Caps of 0 are no caps.
+struct GridCaps {
+    int per_cu = 0;
+    int64_t grid = 0;
+};
+template <class... P, class... A>
+int launch_grid(void (*kernel)(P...), int threads, GridCaps caps, int64_t work_items, int per_ticket, hipStream_t stream, int dev,
+                A... args) {
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0));
+    if (per_cu < 1) per_cu = 1;
+    if (caps.per_cu > 0 && caps.per_cu < per_cu) per_cu = caps.per_cu;
+    const int64_t grid = grid_for(num_cus(dev), per_cu, caps.grid, work_items, per_ticket);
+    if (grid < 1) return 0;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), 0, stream, args...);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 struct BatchView {
     const int64_t* offsets;
     const double* t;
@@ -70,23 +117,8 @@ struct BatchView {
 };
 
 // ---- binning: index lists per LDS tier (feature sets) and per Gram-matrix tier (GP)
-constexpr int kNumBins = 7;            // up to six tiers + "longer than the largest tier" (bin 6; the sets use bins 0..4 + 6)
+// (the lists, the slots of the counts and tickets and the regions behind them: workspace.hpp)
 constexpr int kBinThreads = 1024;
-constexpr int kNumLists = 2 * kNumBins + 12 + 6;
-constexpr int kStatFallbackList = 2 * kNumBins;   // objects the lean statistics kernel hands to the general one
-constexpr int kBazinFallbackList = 2 * kNumBins + 1;   // objects with a band longer than the largest fit tier
-constexpr int kPowerlawFallbackList = 2 * kNumBins + 2;
-constexpr int kStatRetryList = 2 * kNumBins + 3;      // light curves of up to 512 rows the lanes kernels do not take (stat_plan_kernel)
-constexpr int kStatL16List = 2 * kNumBins + 4;        // light curves of up to 128 rows whose bands fit 16-row lanes (r, i: 32 rows)
-constexpr int kStatL32List = 2 * kNumBins + 5;        // ... 32-row lanes (r, i: 64 rows)
-constexpr int kStatL32xList = 2 * kNumBins + 6;       // light curves of up to 256 rows whose bands fit 32-row lanes
-constexpr int kStatW16List = 2 * kNumBins + 7;        // ... up to 256 rows, 32-row lanes with 16 lanes per light curve (bands of up to 64 rows, r, i: 128)
-constexpr int kStatW32List = 2 * kNumBins + 8;        // ... up to 512 rows, the same
-constexpr int kBazinLongList = 2 * kNumBins + 9;      // light curves of more than 1024 rows with a band beyond the largest fit tier
-constexpr int kPowerlawLongList = 2 * kNumBins + 10;  // ... with more post-peak rows in a band than the largest fit tier
-constexpr int kResearchLongList = 2 * kNumBins + 11;  // light curves whose r band spans more days than the Mexican-hat grid in LDS
-static_assert(SetTraits<SET_RESEARCH>::overflow_list == kResearchLongList, "the research set's overflow list");
-constexpr int kGpSortedList = 2 * kNumBins + 12;      // + tier (0..5): the 2-D GP tier's light curves, longest first (gp_sort_kernel)
 struct Bins {
     int* lists;                        // [kNumLists][n_obj]: set tiers, GP tiers, statistics fallback
     int* counts;                       // [kNumLists]
@@ -95,6 +127,8 @@ struct Bins {
 
 // What every launcher of a set gets, built once per set by lcfe_extract_device: the batch and its bins, where the set's
 // columns and status words go, its stream, and its share of the workspace; the launchers are its members.
+struct FitWs;
+struct PlWs;
 struct SetLaunch {
     const BatchView& B;
     const Bins& bins;
@@ -108,13 +142,19 @@ struct SetLaunch {
     int* n_launch;
     unsigned long long* tickets;
     char* long_slabs;
-    // the five sets with launch sequences of their own (+ their extras), and every other set
+    // the five sets with launch sequences of their own, and every other set
     int launch_stat(hipStream_t s1, hipStream_t s2) const;
-    int launch_bazin(void* ws, size_t ws_bytes, int64_t n_points) const;
-    int launch_powerlaw(void* ws, size_t ws_bytes, int64_t n_points) const;
-    int launch_gp(const hipStream_t* gs, int ngs, double* kscratch, size_t kscratch_bytes) const;
+    int launch_bazin(const FitWs& F) const;
+    int launch_powerlaw(const PlWs& F) const;
+    int launch_gp(const hipStream_t* gs, int ngs, double* const* kslab) const;
     int launch_gp1d(double* kslab) const;
     template <int SET> int launch_set() const;
+    // single launches (launch_grid): they spread the fields above into the kernel's arguments
+    template <int SET, int CAP> int tier(int bin, int nan_from, hipStream_t q, unsigned long long* tk, int64_t cap = 0) const;
+    template <int SET> int long_tier(int l0, int l1, int l2) const;
+    template <int CAP> int stat_lean(int bin, hipStream_t q, unsigned long long* tk, int64_t cap = 0) const;
+    template <int NP, bool GLOBAL_K> int gp_tier(int ti, int nan_from, hipStream_t q, double* kscratch, int64_t cap) const;
+    template <int NP, int ROWCAP, int T, int WNP, int MW> int gp1d_tier(int ti, int nan_from, double* kslab = nullptr) const;
 };
 
 __device__ __forceinline__ int set_bin_of(int64_t n) {
@@ -357,12 +397,11 @@ __global__ __launch_bounds__(64) void set_long_kernel(BatchView B, Bins bins, in
     }
 }
 
+// (the set's eighth ticket counter; the callers have checked that the workspace holds the slabs)
 template <int SET>
-int launch_long(const BatchView& B, const Bins& bins, int l0, int l1, int l2, double* out, int ld, int col0, int32_t* status, int st_ld,
-                int st0, hipStream_t stream, unsigned long long* ticket, char* slabs) {
-    if (!slabs) return 0;
+int SetLaunch::long_tier(int l0, int l1, int l2) const {
     hipLaunchKernelGGL(set_long_kernel<SET>, dim3(kLongGrid), dim3(64), 0, stream, B, bins, l0, l1, l2, out, ld, col0, status, st_ld, st0,
-                       ticket, slabs);
+                       tickets + SetTraits<SET>::ticket_base + 7, long_slabs);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -549,13 +588,7 @@ __global__ __launch_bounds__(kPlanThreads) void stat_plan_kernel(BatchView B, Bi
 // wave-uniform scalar work that every lane of its group repeats, so a group of half the width halves it per fit, and
 // wave.hpp's virtual lanes keep every sum in the order of the 8-lane group -- the results are bit-identical.  Tier 0 has
 // no launch of its own: the kernel of the 32-row tier serves both lists (see bazin_fit_kernel).
-constexpr int kFitTiers = 5;
-constexpr int kFitCaps[kFitTiers] = {16, 32, 64, 128, 256}; // rows of one band
-constexpr int kFitCountBase = 32;                           // counts[32 + t]: length of fit list t
-// (the ticket counters of the fit lists sit behind those of the numbered sets and the extension set: 8 per set, 13 sets;
-// the registered sets, bits 14 on, have theirs behind the bin counts -- SetTraits::ticket_base)
-constexpr int kFitTicketBase = 112;                         // tickets[112 + t]
-static_assert(kFitTicketBase >= (SET_ADVANCED + 1) * 8, "fit tickets behind the sets' tickets");
+constexpr int kFitCaps[kFitTiers] = {16, 32, 64, 128, 256}; // rows of one band (count and ticket slots of the lists: workspace.hpp)
 // tier of a band of m rows (m <= 256); narrow == 0 queues the bands of up to 16 rows on the 32-row list (LCFE_FIT_NARROW=0)
 __device__ __forceinline__ int fit_tier_of(int m, int narrow) {
     return (m <= 16) ? (narrow ? 0 : 1) : ((m <= 32) ? 1 : ((m <= 64) ? 2 : ((m <= 128) ? 3 : 4)));
@@ -774,11 +807,6 @@ __global__ __launch_bounds__(256) void bazin_cross_kernel(BatchView B, double* o
 // per object and band g/r/i, the post-peak rows (times relative to the peak, fluxes) and their peak flux and total
 // sum of squares, and queues the band's nine fits: the seven power laws (two parameters, the exponent is data) in
 // list A, the exponential and the linear model (three parameters) in list B, per tier of the post-peak row count.
-constexpr int kPlCountA = 40, kPlCountB = 48;               // counts[40 + t], counts[48 + t]
-constexpr int kPlTicketA = kFitTicketBase + kFitTiers, kPlTicketB = kPlTicketA + kFitTiers;     // tickets[...]
-static_assert(kFitCountBase >= kNumLists && kFitCountBase + kFitTiers <= kPlCountA && kPlCountA + kFitTiers <= kPlCountB && kPlCountB + kFitTiers <= 256,
-              "count slots of the fit lists");
-static_assert(kPlTicketB + kFitTiers <= 128, "ticket slots of the fit lists");
 struct PlWs {
     double* tp;            // post-peak times of band j of object i at offsets[i] + boff[j + 1] ..., indexed like the CSR arrays
     double* fp;
@@ -964,8 +992,6 @@ __global__ __launch_bounds__(64, (BCAP <= 64 ? 2 : 1)) void powerlaw_fit_kernel(
     }
 }
 
-int num_cus(int dev);
-
 // ---- 2-D GP: one light curve per workgroup (256/512/1024 threads by tier); Gram matrix as 16x16
 // lower-triangle tiles in LDS (NP <= 160) or, for longer light curves, in a per-workgroup slab of
 // global scratch.  Objects come from the tier's index list through a ticket counter (one object per
@@ -983,7 +1009,6 @@ constexpr bool kGp112Global = true, kGp160Global = false;
 constexpr int kGp112Grid = 1024, kGp160Grid = 512;
 constexpr size_t kGp112Bytes = kGp112Global ? (size_t)kGp112Grid * gp_store_doubles(112) * 8 : 0;
 constexpr size_t kGp160Bytes = kGp160Global ? (size_t)kGp160Grid * gp_store_doubles(160) * 8 : 0;
-constexpr size_t kGpScratchBytes = kGpSmallBytes + kGpMidBytes + kGpGlobalBytes + kGp112Bytes + kGp160Bytes;
 
 template <int NP> struct gp_threads { static constexpr int T = (NP >= 768) ? 1024 : ((NP >= 160) ? 512 : 256); };
 // the two global-scratch tiers whose second pivot panel fits LDS sweep two pivot tiles per pass over the matrix
@@ -1115,59 +1140,35 @@ __global__ __launch_bounds__(kGpSortThreads) void gp_sort_kernel(const int64_t* 
     }
 }
 
+static_assert(kGpCaps[3] == kGpSmallNP - 1 && kGpCaps[4] == kGpMidNP - 1 && kGpCaps[5] == kGpGlobalNP - 1, "gp_bin_of and workspace.hpp");
+
 template <int NP, bool GLOBAL_K>
-int launch_gp_tier(const BatchView& B, const Bins& bins, int bin, int nan_from, double* out, int ld, int col0,
-                   int32_t* status, int st_ld, int st0, hipStream_t stream, int dev, double* kscratch,
-                   unsigned long long* ticket, int64_t grid_cap = 0) {
-    int per_cu = 0;
-    constexpr int threads = gp_threads<NP>::T;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gp_kernel<NP, GLOBAL_K>, threads, 0));
-    if (per_cu < 1) per_cu = 1;
-    int64_t grid = (int64_t)num_cus(dev) * per_cu;
-    if (GLOBAL_K && grid > gp_grid_cap<NP>::G) grid = gp_grid_cap<NP>::G;
-    if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
+int SetLaunch::gp_tier(int ti, int nan_from, hipStream_t q, double* kscratch, int64_t cap) const {
+    if (GLOBAL_K && (cap < 1 || cap > gp_grid_cap<NP>::G)) cap = gp_grid_cap<NP>::G;     // one slab of global scratch per workgroup
     {
         // tuning knob: LCFE_GP_GRID_<rows>=k caps the workgroups of a tier (fewer Gram matrices in flight = more of them in L2)
         char name[40];
         snprintf(name, sizeof name, "LCFE_GP_GRID_%d", NP);
         const char* e = getenv(name);
-        if (e && atoi(e) > 0 && atoi(e) < grid) grid = atoi(e);
+        if (e && atoi(e) > 0 && (cap < 1 || atoi(e) < cap)) cap = atoi(e);
     }
-    if (grid > B.n_obj) grid = B.n_obj;
-    if (grid < 1) return 0;
-    hipLaunchKernelGGL((gp_kernel<NP, GLOBAL_K>), dim3((unsigned)grid), dim3(threads), 0, stream, B, bins, bin, nan_from,
-                       out, ld, col0, status, st_ld, st0, kscratch, ticket);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_grid(gp_kernel<NP, GLOBAL_K>, gp_threads<NP>::T, {0, cap}, B.n_obj, 1, q, dev, B, bins, ti, nan_from, out, ld, col0, status,
+                       st_ld, st0, kscratch, tickets + SET_GP2D * 8 + ti);
 }
 
-int SetLaunch::launch_gp(const hipStream_t* gs, int ngs, double* kscratch, size_t kscratch_bytes) const {
+// kslab: the Gram-matrix slabs of the tiers in global scratch, in workspace order (WS_GP_SMALL .. WS_GP_160)
+int SetLaunch::launch_gp(const hipStream_t* gs, int ngs, double* const* kslab) const {
     hipStream_t stream2 = gs[(ngs > 1) ? 1 : 0];
     // (A variant that keeps the matrix in the REGISTERS of the workgroup -- 2-D block-cyclic tiles,
     // register-tiled outer products -- was built and measured: slower on every tier, because hipcc
     // spends 412-512 registers per lane on the unrolled tile passes and spills at 1024 threads.)
-    const int caps[6] = {63, 111, 159, kGpSmallNP - 1, kGpMidNP - 1, kGpGlobalNP - 1};
-    int last = 0;
-    while (last < 5 && caps[last] < max_len) ++last;
-    if (kscratch_bytes < kGpScratchBytes)
-        return fail_msg("lcfe_extract_device: workspace too small for the GP global tiers");
-    double* k_small = kscratch;
-    double* k_mid = kscratch + kGpSmallBytes / 8;
-    double* k_glob = k_mid + kGpMidBytes / 8;
-    double* k_112 = k_glob + kGpGlobalBytes / 8;
-    double* k_160 = k_112 + kGp112Bytes / 8;
+    const int last = gp_last_tier(max_len);
     // every tier's list longest light curve first (on the first GP stream; the others wait for it)
     {
         hipLaunchKernelGGL(gp_sort_kernel, dim3((unsigned)(last + 1)), dim3(kGpSortThreads), 0, gs[0], B.offsets, bins);
         HIP_TRY(hipGetLastError());
         ++*n_launch;
-        if (ngs > 1) {
-            hipEvent_t sorted;
-            HIP_TRY(hipEventCreateWithFlags(&sorted, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(sorted, gs[0]));
-            for (int k = 1; k < ngs; ++k) HIP_TRY(hipStreamWaitEvent(gs[k], sorted, 0));
-            (void)hipEventDestroy(sorted);
-        }
+        if (ngs > 1 && stream_wait(gs + 1, ngs - 1, gs[0])) return 1;
     }
     // Launch plan: which stream takes which tiers, in which order, and on how many workgroups at most.  Default (two GP
     // streams): longest tier first, tiers alternating between the streams -- the heavy-tailed end of one tier (single objects
@@ -1203,17 +1204,16 @@ int SetLaunch::launch_gp(const hipStream_t* gs, int ngs, double* kscratch, size_
     for (int pi = 0; pi < n_plan; ++pi) {
         const int ti = plan[pi].tier;
         const int64_t cap = plan[pi].cap;
-        const int nan_from = (ti == last) ? ti + 1 : kNumBins;
-        unsigned long long* tk = tickets + SET_GP2D * 8 + ti;
+        const int nan_from = nan_from_of(ti, last);
         hipStream_t q = gs[plan[pi].stream];
         int rc = 0;
         switch (ti) {
-            case 0: rc = launch_gp_tier<64, false>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, q, dev, nullptr, tk, cap); break;
-            case 1: rc = launch_gp_tier<112, kGp112Global>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, q, dev, k_112, tk, cap); break;
-            case 2: rc = launch_gp_tier<160, kGp160Global>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, q, dev, k_160, tk, cap); break;
-            case 3: rc = launch_gp_tier<kGpSmallNP, true>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, q, dev, k_small, tk, cap); break;
-            case 4: rc = launch_gp_tier<kGpMidNP, true>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, q, dev, k_mid, tk, cap); break;
-            case 5: rc = launch_gp_tier<kGpGlobalNP, true>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, q, dev, k_glob, tk, cap); break;
+            case 0: rc = gp_tier<64, false>(ti, nan_from, q, nullptr, cap); break;
+            case 1: rc = gp_tier<112, kGp112Global>(ti, nan_from, q, kslab[3], cap); break;
+            case 2: rc = gp_tier<160, kGp160Global>(ti, nan_from, q, kslab[4], cap); break;
+            case 3: rc = gp_tier<kGpSmallNP, true>(ti, nan_from, q, kslab[0], cap); break;
+            case 4: rc = gp_tier<kGpMidNP, true>(ti, nan_from, q, kslab[1], cap); break;
+            case 5: rc = gp_tier<kGpGlobalNP, true>(ti, nan_from, q, kslab[2], cap); break;
         }
         if (rc) return rc;
         ++*n_launch;
@@ -1396,21 +1396,11 @@ __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int
     nan_fill_bins<W>(bins, 1, nan_from, out, ld, col0, GP1D_NCOL, status, st_ld, st0, GP1D_NSTATUS);
 }
 
+// (kslab: one slab of global scratch per workgroup)
 template <int NP, int ROWCAP, int T, int WNP, int MW>
-int launch_gp1d_tier(const BatchView& B, const Bins& bins, int bin, int nan_from, double* out, int ld, int col0,
-                     int32_t* status, int st_ld, int st0, hipStream_t stream, int dev, unsigned long long* ticket,
-                     double* kslab = nullptr) {
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gp1d_kernel<NP, ROWCAP, T, WNP, MW>, T, 0));
-    if (per_cu < 1) per_cu = 1;
-    int64_t grid = (int64_t)num_cus(dev) * per_cu;
-    if (kslab && grid > kGp1dLongGrid) grid = kGp1dLongGrid;        // one slab of global scratch per workgroup
-    if (grid > B.n_obj) grid = B.n_obj;
-    if (grid < 1) return 0;
-    hipLaunchKernelGGL((gp1d_kernel<NP, ROWCAP, T, WNP, MW>), dim3((unsigned)grid), dim3(T), 0, stream, B, bins, bin, nan_from, out, ld,
-                       col0, status, st_ld, st0, ticket, kslab);
-    HIP_TRY(hipGetLastError());
-    return 0;
+int SetLaunch::gp1d_tier(int ti, int nan_from, double* kslab) const {
+    return launch_grid(gp1d_kernel<NP, ROWCAP, T, WNP, MW>, T, {0, kslab ? kGp1dLongGrid : 0}, B.n_obj, 1, stream, dev, B, bins, ti, nan_from, out,
+                       ld, col0, status, st_ld, st0, tickets + SET_GP1D * 8 + ti, kslab);
 }
 
 // ---- the long-object tier of the per-band GP: light curves of more than 767 rows (GP bin 6), up to kLongCap rows, each band
@@ -1553,18 +1543,15 @@ __global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B,
 // global scratch; bin 6 (more than 767 rows) in the long-object tier when the workspace holds its slabs (long_slab),
 // NaN and status -100 otherwise.
 int SetLaunch::launch_gp1d(double* kslab) const {
-    const int caps[6] = {63, 111, 159, kGpSmallNP - 1, kGpMidNP - 1, kGpGlobalNP - 1};
-    int last = 0;
-    while (last < 5 && caps[last] < max_len) ++last;
+    const int last = gp_last_tier(max_len);
     for (int ti = last; ti >= 0; --ti) {
-        const int nan_from = (ti == last) ? ti + 1 : kNumBins;
-        unsigned long long* tk = tickets + SET_GP1D * 8 + ti;
+        const int nan_from = nan_from_of(ti, last);
         int rc = 0;
         switch (ti) {
-            case 0: rc = launch_gp1d_tier<64, 64, kGp1dThreads, 32, 3>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk); break;
-            case 1: rc = launch_gp1d_tier<112, 112, kGp1dThreads, 32, 2>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk); break;
-            case 2: rc = launch_gp1d_tier<160, 160, kGp1dThreads, 64, 1>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk); break;
-            default: rc = launch_gp1d_tier<160, 768, kGp1dThreads, 64, 1>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk, kslab); break;
+            case 0: rc = gp1d_tier<64, 64, kGp1dThreads, 32, 3>(ti, nan_from); break;
+            case 1: rc = gp1d_tier<112, 112, kGp1dThreads, 32, 2>(ti, nan_from); break;
+            case 2: rc = gp1d_tier<160, 160, kGp1dThreads, 64, 1>(ti, nan_from); break;
+            default: rc = gp1d_tier<160, 768, kGp1dThreads, 64, 1>(ti, nan_from, kslab); break;
         }
         if (rc) return rc;
         ++*n_launch;
@@ -1581,82 +1568,34 @@ int SetLaunch::launch_gp1d(double* kslab) const {
     return 0;
 }
 
-// ticket counters of the registered sets (SetTraits::ticket_base): tickets[256] on, behind the bin counts
-constexpr int kRegTicketBase = 256, kRegTicketSets = 4;
-static_assert(SetTraits<SET_CESIUM>::ticket_base == kRegTicketBase && NUM_ALL_SETS - SET_CESIUM <= kRegTicketSets,
-              "ticket counters of the registered sets");
-
-
-int g_num_cu[16] = {0};
-std::mutex g_num_cu_mutex;
-
-int num_cus(int dev) {
-    if (dev < 0 || dev >= 16) return 256;
-    std::lock_guard<std::mutex> lock(g_num_cu_mutex);
-    if (!g_num_cu[dev]) {
-        hipDeviceProp_t p;
-        if (hipGetDeviceProperties(&p, dev) == hipSuccess) g_num_cu[dev] = p.multiProcessorCount;
-        else g_num_cu[dev] = 256;
-    }
-    return g_num_cu[dev];
-}
-
 template <int SET, int CAP>
-int launch_tier(const BatchView& B, const Bins& bins, int bin, int nan_from, double* out, int ld, int col0,
-                int32_t* status, int st_ld, int st0, hipStream_t stream, int dev, unsigned long long* ticket,
-                int64_t max_grid = 1 << 30) {
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, set_kernel<SET, CAP>, 64, 0));
-    if (per_cu < 1) per_cu = 1;
-    int64_t grid = (int64_t)num_cus(dev) * per_cu;
-    if (grid > max_grid) grid = max_grid;
-    const int chunk = SetTraits<SET>::chunk;
-    if (grid * chunk > B.n_obj) grid = (B.n_obj + chunk - 1) / chunk;
-    if (grid < 1) return 0;
-    hipLaunchKernelGGL((set_kernel<SET, CAP>), dim3((unsigned)grid), dim3(64), 0, stream, B, bins, bin, nan_from,
-                       out, ld, col0, status, st_ld, st0, ticket, chunk);
-    HIP_TRY(hipGetLastError());
-    return 0;
+int SetLaunch::tier(int bin, int nan_from, hipStream_t q, unsigned long long* tk, int64_t cap) const {
+    constexpr int chunk = SetTraits<SET>::chunk;
+    return launch_grid(set_kernel<SET, CAP>, 64, {0, cap}, B.n_obj, chunk, q, dev, B, bins, bin, nan_from, out, ld, col0, status, st_ld, st0,
+                       tk, chunk);
 }
 
 template <int SET>
 int SetLaunch::launch_set() const {
     using T = SetTraits<SET>;
-    // tiers needed: every tier whose window (prev_cap, cap] can contain an object, i.e. up to the
-    // first cap >= max_len; the last launched tier also NaN-fills the bins of longer objects.
-    int last = 0;
-    while (last < T::max_tier && kTiers[last] < max_len) ++last;
+    const int last = last_tier(max_len, T::max_tier);
     for (int ti = 0; ti <= last; ++ti) {
-        const int nan_from = (ti == last) ? ti + 1 : kNumBins;
-        unsigned long long* tk = tickets + T::ticket_base + ti;
-        int rc = 0;
-        switch (ti) {
-            case 0: rc = launch_tier<SET, 128>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk); break;
-            case 1: rc = launch_tier<SET, 256>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk); break;
-            case 2: rc = launch_tier<SET, 512>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk); break;
-            case 3: rc = launch_tier<SET, 1024>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk); break;
-            case 4:
-                if constexpr (T::max_tier >= 4)
-                    rc = launch_tier<SET, 2048>(B, bins, ti, nan_from, out, ld, col0, status, st_ld, st0, stream, dev, tk);
-                break;
-        }
+        const int rc = for_tier(ti, [&](auto cap) -> int {
+            if constexpr (cap() <= kTiers[T::max_tier])      // (no 2048-row kernel for a set whose tiers end at 1024 rows)
+                return this->template tier<SET, cap()>(ti, nan_from_of(ti, last), stream, tickets + T::ticket_base + ti);
+            return 0;
+        });
         if (rc) return rc;
         ++*n_launch;
     }
     // the long-object tier: bin 6 (more than 2048 rows), bin 4 too where the set's LDS tiers end at 1024 rows, and the set's
     // overflow list (research: more than 4096 days of r band)
     if (long_slabs && (max_len > T::long_above || T::overflow_list >= 0)) {
-        const int rc = launch_long<SET>(B, bins, 6, (T::max_tier < 4) ? 4 : -1, T::overflow_list, out, ld, col0,
-                                        status, st_ld, st0, stream, tickets + T::ticket_base + 7, long_slabs);
+        const int rc = long_tier<SET>(6, (T::max_tier < 4) ? 4 : -1, T::overflow_list);
         if (rc) return rc;
         ++*n_launch;
     }
     return 0;
-}
-
-size_t bazin_ws_bytes(int64_t n_obj, int64_t n_points) {
-    const size_t np = (size_t)(n_points > 0 ? n_points : 1), no = (size_t)(n_obj > 0 ? n_obj : 1);
-    return ((3 * 8 * np + 255) & ~(size_t)255) + ((32 * no + 255) & ~(size_t)255) + ((4 * (size_t)kFitTiers * 6 * no + 255) & ~(size_t)255);
 }
 
 // LCFE_FIT_NARROW=0 queues the bands of up to 16 rows on the 32-row fit lists, as before the 16-row tier (A/B measurements)
@@ -1665,89 +1604,45 @@ static bool fit_narrow_enabled() {
     return on;
 }
 
-template <int CAP>
-int launch_bazin_partition(const BatchView& B, const Bins& bins, int bin, int nan_from, const FitWs& F, double* out, int ld, int col0,
-                           int32_t* status, int st_ld, int st0, hipStream_t stream, int dev, unsigned long long* ticket) {
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bazin_partition_kernel<CAP>, 64, 0));
-    if (per_cu < 1) per_cu = 1;
-    int64_t grid = (int64_t)num_cus(dev) * per_cu;
-    if (grid * 8 > B.n_obj) grid = (B.n_obj + 7) / 8;
-    if (grid < 1) return 0;
-    hipLaunchKernelGGL((bazin_partition_kernel<CAP>), dim3((unsigned)grid), dim3(64), 0, stream, B, bins, bin, nan_from, F, out, ld, col0,
-                       status, st_ld, st0, ticket, 8, fit_narrow_enabled() ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 // tuning knob: LCFE_FIT_WAVES_<rows>=k caps the fit kernels of that band-length tier at k wavefronts per CU (their LDS
-// regions otherwise take most of a CU and keep the LDS-resident GP tiers off it)
-static int fit_waves_cap(int bcap, int per_cu) {
+// regions otherwise take most of a CU and keep the LDS-resident GP tiers off it); 0: no cap
+static int fit_waves_cap(int bcap) {
     char name[40];
     snprintf(name, sizeof name, "LCFE_FIT_WAVES_%d", bcap);
     const char* e = getenv(name);
-    if (e && atoi(e) > 0 && atoi(e) < per_cu) return atoi(e);
-    return per_cu;
-}
-
-template <int BCAP>
-int launch_bazin_fits(const BatchView& B, const Bins& bins, const FitWs& F, int tier, double* out, int ld, int col0, int32_t* status,
-                      int st_ld, int st0, hipStream_t stream, int dev, unsigned long long* ticket, unsigned long long* ticket_narrow) {
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bazin_fit_kernel<BCAP>, 64, 0));
-    if (per_cu < 1) per_cu = 1;
-    per_cu = fit_waves_cap(BCAP, per_cu);
-    int64_t grid = (int64_t)num_cus(dev) * per_cu;
-    if (grid * 8 > 6 * B.n_obj) grid = (6 * B.n_obj + 7) / 8;
-    if (grid < 1) return 0;
-    hipLaunchKernelGGL((bazin_fit_kernel<BCAP>), dim3((unsigned)grid), dim3(64), 0, stream, B, bins, F, tier, out, ld, col0, status,
-                       st_ld, st0, ticket, ticket_narrow);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return (e && atoi(e) > 0) ? atoi(e) : 0;
 }
 
 // Bazin: partition pass per object tier, the fit kernel per band-length tier (longest first), the object-level
 // kernel for objects with a band beyond the largest fit tier, then the cross-band columns.
-int SetLaunch::launch_bazin(void* ws, size_t ws_bytes, int64_t n_points) const {
-    if (!ws || ws_bytes < bazin_ws_bytes(B.n_obj, n_points))
-        return fail_msg("lcfe_extract_device: workspace too small for the Bazin fit lists");
-    const size_t np = (size_t)(n_points > 0 ? n_points : 1), no = (size_t)B.n_obj;
-    FitWs F;
-    char* p = (char*)ws;
-    F.pt = (double*)p; F.pf = F.pt + np; F.pe = F.pf + np;
-    p += (3 * 8 * np + 255) & ~(size_t)255;
-    F.pboff = (int*)p;
-    p += (32 * no + 255) & ~(size_t)255;
-    F.fits = (int*)p;
-    F.fit_stride = 6 * (int64_t)no;
-    int last = 0;
-    while (last < 4 && kTiers[last] < max_len) ++last;
+int SetLaunch::launch_bazin(const FitWs& F) const {
+    const int last = last_tier(max_len, 4);
     unsigned long long* tk = tickets + SET_BAZIN * 8;
     for (int ti = 0; ti <= last; ++ti) {
-        const int nan_from = (ti == last) ? ti + 1 : kNumBins;
-        int rc = 0;
-        switch (ti) {
-            case 0: rc = launch_bazin_partition<128>(B, bins, ti, nan_from, F, out, ld, col0, status, st_ld, st0, stream, dev, tk + ti); break;
-            case 1: rc = launch_bazin_partition<256>(B, bins, ti, nan_from, F, out, ld, col0, status, st_ld, st0, stream, dev, tk + ti); break;
-            case 2: rc = launch_bazin_partition<512>(B, bins, ti, nan_from, F, out, ld, col0, status, st_ld, st0, stream, dev, tk + ti); break;
-            case 3: rc = launch_bazin_partition<1024>(B, bins, ti, nan_from, F, out, ld, col0, status, st_ld, st0, stream, dev, tk + ti); break;
-            case 4: rc = launch_bazin_partition<2048>(B, bins, ti, nan_from, F, out, ld, col0, status, st_ld, st0, stream, dev, tk + ti); break;
-        }
+        const int rc = for_tier(ti, [&](auto cap) {
+            return launch_grid(bazin_partition_kernel<cap()>, 64, {}, B.n_obj, 8, stream, dev, B, bins, ti, nan_from_of(ti, last), F, out, ld,
+                               col0, status, st_ld, st0, tk + ti, 8, fit_narrow_enabled() ? 1 : 0);
+        });
         if (rc) return rc;
         ++*n_launch;
     }
     // objects with a band of more than 256 rows: the object-level kernel (all 52 columns).  A small grid, and AHEAD of the
     // fit tiers: the list is normally empty, but every workgroup of this kernel needs 136 KiB of LDS -- at the end of the
     // stream it sat in the dispatcher for 100-180 ms, until a GP tier released a whole CU (tools/step_timeline.py)
-    int rc = launch_tier<SET_BAZIN, 1024>(B, bins, kBazinFallbackList, kNumBins, out, ld, col0, status, st_ld, st0, stream, dev, tk + 5, 32);
+    int rc = tier<SET_BAZIN, 1024>(kBazinFallbackList, kNumBins, stream, tk + 5, 32);
     if (rc) return rc;
     ++*n_launch;
-    // (the 32-row launch serves the 16-row list as well: tier 0 has no kernel of its own)
+    // one ticket = 8 fits; (the 32-row launch serves the 16-row list as well: tier 0 has no kernel of its own)
     unsigned long long* ftk = tickets + kFitTicketBase;
-    rc = launch_bazin_fits<256>(B, bins, F, 4, out, ld, col0, status, st_ld, st0, stream, dev, ftk + 4, ftk);
-    if (!rc) rc = launch_bazin_fits<128>(B, bins, F, 3, out, ld, col0, status, st_ld, st0, stream, dev, ftk + 3, ftk);
-    if (!rc) rc = launch_bazin_fits<64>(B, bins, F, 2, out, ld, col0, status, st_ld, st0, stream, dev, ftk + 2, ftk);
-    if (!rc) rc = launch_bazin_fits<32>(B, bins, F, 1, out, ld, col0, status, st_ld, st0, stream, dev, ftk + 1, ftk);
+    auto fits = [&](auto t) {
+        constexpr int T = t(), BCAP = kFitCaps[T];
+        return launch_grid(bazin_fit_kernel<BCAP>, 64, {fit_waves_cap(BCAP), 0}, kBazinFits * B.n_obj, 8, stream, dev, B, bins, F, T, out, ld,
+                           col0, status, st_ld, st0, ftk + T, ftk);
+    };
+    rc = fits(IntTag<4>{});
+    if (!rc) rc = fits(IntTag<3>{});
+    if (!rc) rc = fits(IntTag<2>{});
+    if (!rc) rc = fits(IntTag<1>{});
     if (rc) return rc;
     *n_launch += 4;
     hipLaunchKernelGGL(bazin_cross_kernel, dim3((unsigned)((B.n_obj + 255) / 256)), dim3(256), 0, stream, B, out, ld, col0);
@@ -1755,116 +1650,56 @@ int SetLaunch::launch_bazin(void* ws, size_t ws_bytes, int64_t n_points) const {
     ++*n_launch;
     // the long-object tier: more than 2048 rows (bin 6), or more than 1024 rows with a band beyond the fit tiers (all 52 columns)
     if (long_slabs && max_len > SetTraits<SET_BAZIN>::long_above) {
-        rc = launch_long<SET_BAZIN>(B, bins, 6, kBazinLongList, -1, out, ld, col0, status, st_ld, st0, stream, tk + 7, long_slabs);
+        rc = long_tier<SET_BAZIN>(6, kBazinLongList, -1);
         if (rc) return rc;
         ++*n_launch;
     }
     return 0;
 }
 
-size_t powerlaw_ws_bytes(int64_t n_obj, int64_t n_points) {
-    const size_t np = (size_t)(n_points > 0 ? n_points : 1), no = (size_t)(n_obj > 0 ? n_obj : 1);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    return al(2 * 8 * np) + al(2 * 3 * 8 * no) + al(32 * no) + al(12 * no) + al(4 * (size_t)kFitTiers * 21 * no) + al(4 * (size_t)kFitTiers * 6 * no);
-}
-
-template <int CAP>
-int launch_powerlaw_partition(const BatchView& B, const Bins& bins, int bin, int nan_from, const PlWs& F, double* out, int ld, int col0,
-                              int32_t* status, int st_ld, int st0, hipStream_t stream, int dev, unsigned long long* ticket) {
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, powerlaw_partition_kernel<CAP>, 64, 0));
-    if (per_cu < 1) per_cu = 1;
-    int64_t grid = (int64_t)num_cus(dev) * per_cu;
-    if (grid * 8 > B.n_obj) grid = (B.n_obj + 7) / 8;
-    if (grid < 1) return 0;
-    hipLaunchKernelGGL((powerlaw_partition_kernel<CAP>), dim3((unsigned)grid), dim3(64), 0, stream, B, bins, bin, nan_from, F, out, ld,
-                       col0, status, st_ld, st0, ticket, 8, fit_narrow_enabled() ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-template <int N, int BCAP>
-int launch_powerlaw_fits(const BatchView& B, const Bins& bins, const PlWs& F, int tier, double* out, int ld, int col0, int32_t* status,
-                         int st_ld, int st0, hipStream_t stream, int dev, unsigned long long* ticket, unsigned long long* ticket_narrow) {
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (powerlaw_fit_kernel<N, BCAP>), 64, 0));
-    if (per_cu < 1) per_cu = 1;
-    per_cu = fit_waves_cap(BCAP, per_cu);
-    int64_t grid = (int64_t)num_cus(dev) * per_cu;
-    const int64_t nfit = ((N == 2) ? 21 : 6) * B.n_obj;
-    if (grid * 8 > nfit) grid = (nfit + 7) / 8;
-    if (grid < 1) return 0;
-    hipLaunchKernelGGL((powerlaw_fit_kernel<N, BCAP>), dim3((unsigned)grid), dim3(64), 0, stream, B, bins, F, tier, out, ld, col0, status,
-                       st_ld, st0, ticket, ticket_narrow);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int SetLaunch::launch_powerlaw(void* ws, size_t ws_bytes, int64_t n_points) const {
-    if (!ws || ws_bytes < powerlaw_ws_bytes(B.n_obj, n_points))
-        return fail_msg("lcfe_extract_device: workspace too small for the decline-fit lists");
-    const size_t np = (size_t)(n_points > 0 ? n_points : 1), no = (size_t)B.n_obj;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    PlWs F;
-    char* p = (char*)ws;
-    F.tp = (double*)p; F.fp = F.tp + np; p += al(2 * 8 * np);
-    F.peak = (double*)p; F.sstot = F.peak + 3 * no; p += al(2 * 3 * 8 * no);
-    F.pboff = (int*)p; p += al(32 * no);
-    F.kk = (int*)p; p += al(12 * no);
-    F.fitsA = (int*)p; p += al(4 * (size_t)kFitTiers * 21 * no);
-    F.fitsB = (int*)p;
-    F.strideA = 21 * (int64_t)no;
-    F.strideB = 6 * (int64_t)no;
-    int last = 0;
-    while (last < 4 && kTiers[last] < max_len) ++last;
+int SetLaunch::launch_powerlaw(const PlWs& F) const {
+    const int last = last_tier(max_len, 4);
     unsigned long long* tk = tickets + SET_POWERLAW * 8;
     for (int ti = 0; ti <= last; ++ti) {
-        const int nan_from = (ti == last) ? ti + 1 : kNumBins;
-        int rc = 0;
-        switch (ti) {
-            case 0: rc = launch_powerlaw_partition<128>(B, bins, ti, nan_from, F, out, ld, col0, status, st_ld, st0, stream, dev, tk + ti); break;
-            case 1: rc = launch_powerlaw_partition<256>(B, bins, ti, nan_from, F, out, ld, col0, status, st_ld, st0, stream, dev, tk + ti); break;
-            case 2: rc = launch_powerlaw_partition<512>(B, bins, ti, nan_from, F, out, ld, col0, status, st_ld, st0, stream, dev, tk + ti); break;
-            case 3: rc = launch_powerlaw_partition<1024>(B, bins, ti, nan_from, F, out, ld, col0, status, st_ld, st0, stream, dev, tk + ti); break;
-            case 4: rc = launch_powerlaw_partition<2048>(B, bins, ti, nan_from, F, out, ld, col0, status, st_ld, st0, stream, dev, tk + ti); break;
-        }
+        const int rc = for_tier(ti, [&](auto cap) {
+            return launch_grid(powerlaw_partition_kernel<cap()>, 64, {}, B.n_obj, 8, stream, dev, B, bins, ti, nan_from_of(ti, last), F, out, ld,
+                               col0, status, st_ld, st0, tk + ti, 8, fit_narrow_enabled() ? 1 : 0);
+        });
         if (rc) return rc;
         ++*n_launch;
     }
     // the object-level kernel for the (normally empty) list of objects beyond the fit tiers, AHEAD of the fit tiers: see launch_bazin
-    int rc = launch_tier<SET_POWERLAW, 1024>(B, bins, kPowerlawFallbackList, kNumBins, out, ld, col0, status, st_ld, st0, stream, dev, tk + 5, 32);
+    int rc = tier<SET_POWERLAW, 1024>(kPowerlawFallbackList, kNumBins, stream, tk + 5, 32);
     if (rc) return rc;
     ++*n_launch;
-#define PL_TIER(BC, T)                                                                                                        \
-    if (!rc) rc = launch_powerlaw_fits<2, BC>(B, bins, F, T, out, ld, col0, status, st_ld, st0, stream, dev, tickets + kPlTicketA + T, tickets + kPlTicketA); \
-    if (!rc) rc = launch_powerlaw_fits<3, BC>(B, bins, F, T, out, ld, col0, status, st_ld, st0, stream, dev, tickets + kPlTicketB + T, tickets + kPlTicketB);
+    // per band-length tier the two-parameter fits (list A), then the three-parameter ones (list B); one ticket = 8 fits
     // (the 32-row launches serve the 16-row lists as well: tier 0 has no kernels of its own)
-    PL_TIER(256, 4) PL_TIER(128, 3) PL_TIER(64, 2) PL_TIER(32, 1)
-#undef PL_TIER
+    auto fits = [&](auto t) {
+        constexpr int T = t(), BCAP = kFitCaps[T];
+        const int ra = launch_grid(powerlaw_fit_kernel<2, BCAP>, 64, {fit_waves_cap(BCAP), 0}, kPlFitsA * B.n_obj, 8, stream, dev, B, bins, F, T,
+                                   out, ld, col0, status, st_ld, st0, tickets + kPlTicketA + T, tickets + kPlTicketA);
+        if (ra) return ra;
+        return launch_grid(powerlaw_fit_kernel<3, BCAP>, 64, {fit_waves_cap(BCAP), 0}, kPlFitsB * B.n_obj, 8, stream, dev, B, bins, F, T, out,
+                           ld, col0, status, st_ld, st0, tickets + kPlTicketB + T, tickets + kPlTicketB);
+    };
+    rc = fits(IntTag<4>{});
+    if (!rc) rc = fits(IntTag<3>{});
+    if (!rc) rc = fits(IntTag<2>{});
+    if (!rc) rc = fits(IntTag<1>{});
     if (rc) return rc;
     *n_launch += 8;
     if (long_slabs && max_len > SetTraits<SET_POWERLAW>::long_above) {
-        rc = launch_long<SET_POWERLAW>(B, bins, 6, kPowerlawLongList, -1, out, ld, col0, status, st_ld, st0, stream, tk + 7, long_slabs);
+        rc = long_tier<SET_POWERLAW>(6, kPowerlawLongList, -1);
         if (rc) return rc;
         ++*n_launch;
     }
     return 0;
 }
 
+// (cap: for a list expected to be short: every wavefront's first ticket is an atomic on one counter)
 template <int CAP>
-int launch_stat_lean(const BatchView& B, const Bins& bins, int bin, double* out, int ld, int col0, hipStream_t stream,
-                     int dev, unsigned long long* ticket, int64_t grid_cap = 0) {
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, stat_lean_kernel<CAP>, 64, 0));
-    if (per_cu < 1) per_cu = 1;
-    int64_t grid = (int64_t)num_cus(dev) * per_cu;
-    if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;    // a list expected to be short: every wavefront's first ticket is an atomic on one counter
-    if (grid * 8 > B.n_obj) grid = (B.n_obj + 7) / 8;
-    if (grid < 1) return 0;
-    hipLaunchKernelGGL((stat_lean_kernel<CAP>), dim3((unsigned)grid), dim3(64), 0, stream, B, bins, bin, out, ld, col0,
-                       ticket, 8);
-    HIP_TRY(hipGetLastError());
-    return 0;
+int SetLaunch::stat_lean(int bin, hipStream_t q, unsigned long long* tk, int64_t cap) const {
+    return launch_grid(stat_lean_kernel<CAP>, 64, {0, cap}, B.n_obj, 8, q, dev, B, bins, bin, out, ld, col0, tk, 8);
 }
 
 int launch_stat_plan(const BatchView& B, const Bins& bins, hipStream_t stream) {
@@ -1890,8 +1725,10 @@ static bool stat_lanes_enabled() {
 // Statistics: lean kernels for the tiers up to 512 rows, the general kernel for the longer tiers,
 // for the lean kernels' fallback list and for the NaN rows of over-long objects.
 int SetLaunch::launch_stat(hipStream_t s1, hipStream_t s2) const {
-    int last = 0;
-    while (last < 4 && kTiers[last] < max_len) ++last;
+    SetLaunch G = *this;                // the general kernel's launches: the set has no status words
+    G.status = nullptr;
+    G.st_ld = G.st0 = 0;
+    const int last = last_tier(max_len, 4);
     unsigned long long* tk = tickets + SET_STAT * 8;
     // The tier kernels are independent (disjoint objects): with side streams they are enqueued side by side, so the
     // ramp-down of one tier is filled by the waves of the others; they are joined before the fallback launch.
@@ -1900,21 +1737,17 @@ int SetLaunch::launch_stat(hipStream_t s1, hipStream_t s2) const {
     //   s1:     after the plan kernels, the 256-row tier's one-light-curve-per-wavefront kernel
     const bool lanes = stat_lanes_enabled();
     const bool fork = (s1 != stream) && (s2 != stream) && last >= 1;
-    hipEvent_t ev_fork = nullptr, ev_plan = nullptr, ev_j1 = nullptr, ev_j2 = nullptr;
-    struct Cleanup { hipEvent_t* e[4]; ~Cleanup() { for (auto p : e) if (*p) (void)hipEventDestroy(*p); } } cleanup{{&ev_fork, &ev_plan, &ev_j1, &ev_j2}};
     hipStream_t q_long = fork ? s2 : stream, q_mid = fork ? s1 : stream;
-    if (fork) {
-        HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ev_fork, stream));
-        HIP_TRY(hipStreamWaitEvent(s2, ev_fork, 0));
-    }
+    if (fork && stream_wait(s2, stream)) return 1;
     for (int ti = 2; ti <= last; ++ti) {
-        const int nan_from = (ti == last) ? ti + 1 : kNumBins;
         int rc = 0;
-        switch (ti) {
-            case 2: if (!lanes) rc = launch_stat_lean<512>(B, bins, ti, out, ld, col0, q_long, dev, tk + ti); break;   // (else: after its plan kernel)
-            case 3: rc = launch_tier<SET_STAT, 1024>(B, bins, ti, nan_from, out, ld, col0, nullptr, 0, 0, q_long, dev, tk + ti); break;
-            case 4: rc = launch_tier<SET_STAT, 2048>(B, bins, ti, nan_from, out, ld, col0, nullptr, 0, 0, q_long, dev, tk + ti); break;
+        if (ti == 2) {
+            if (!lanes) rc = stat_lean<512>(ti, q_long, tk + ti);   // (else: after its plan kernel)
+        } else {
+            rc = for_tier(ti, [&](auto cap) -> int {
+                if constexpr (cap() > 512) return G.tier<SET_STAT, cap()>(ti, nan_from_of(ti, last), q_long, tk + ti);
+                return 0;
+            });
         }
         if (rc) return rc;
         ++*n_launch;
@@ -1926,48 +1759,39 @@ int SetLaunch::launch_stat(hipStream_t s1, hipStream_t s2) const {
         ++*n_launch;
     }
     if (fork) {
-        HIP_TRY(hipEventCreateWithFlags(&ev_plan, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ev_plan, stream));
-        HIP_TRY(hipStreamWaitEvent(s1, ev_plan, 0));
-        if (lanes && last >= 2) HIP_TRY(hipStreamWaitEvent(s2, ev_plan, 0));
+        const hipStream_t after_plan[2] = {s1, s2};
+        if (stream_wait(after_plan, (lanes && last >= 2) ? 2 : 1, stream)) return 1;
     }
     {
         int rc = 0;
         if (lanes) {
             // what the lanes variants do not take: one light curve per wavefront, sized for the longest tier present;
             // a light curve whose rows turn out not to ascend in time goes to the general kernel's list
-            if (last >= 2) rc = launch_stat_lean<512>(B, bins, kStatRetryList, out, ld, col0, q_long, dev, tk + 2);
-            else if (last == 1) rc = launch_stat_lean<256>(B, bins, kStatRetryList, out, ld, col0, q_mid, dev, tk + 1, 512);
+            if (last >= 2) rc = stat_lean<512>(kStatRetryList, q_long, tk + 2);
+            else if (last == 1) rc = stat_lean<256>(kStatRetryList, q_mid, tk + 1, 512);
             if (!rc) rc = launch_stat_lanes_all(B, bins, kStatFallbackList, out, ld, col0, stream);
-            if (!rc && last < 1) rc = launch_stat_lean<128>(B, bins, kStatRetryList, out, ld, col0, stream, dev, tk + 6, 512);
+            if (!rc && last < 1) rc = stat_lean<128>(kStatRetryList, stream, tk + 6, 512);
             *n_launch += 2;
         } else {
-            if (last >= 1) rc = launch_stat_lean<256>(B, bins, 1, out, ld, col0, q_mid, dev, tk + 1);
-            if (!rc) rc = launch_stat_lean<128>(B, bins, 0, out, ld, col0, stream, dev, tk + 0);
+            if (last >= 1) rc = stat_lean<256>(1, q_mid, tk + 1);
+            if (!rc) rc = stat_lean<128>(0, stream, tk + 0);
             *n_launch += 2;
         }
         if (rc) return rc;
     }
-    if (fork) {
-        HIP_TRY(hipEventCreateWithFlags(&ev_j1, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&ev_j2, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ev_j1, s1));
-        HIP_TRY(hipEventRecord(ev_j2, s2));
-        HIP_TRY(hipStreamWaitEvent(stream, ev_j1, 0));
-        HIP_TRY(hipStreamWaitEvent(stream, ev_j2, 0));
-    }
+    if (fork && (stream_wait(stream, s1) || stream_wait(stream, s2))) return 1;
     // fallback list of the lean tiers (+ the NaN rows when no general tier ran): normally empty or a
     // handful of objects, so a quarter-chip grid keeps the launch short
     const int nan_from = (last <= 2) ? last + 1 : kNumBins;
     const int64_t fb_grid = 256;
-    int rc = 0;
-    if (last == 0) rc = launch_tier<SET_STAT, 128>(B, bins, kStatFallbackList, nan_from, out, ld, col0, nullptr, 0, 0, stream, dev, tk + 5, fb_grid);
-    else if (last == 1) rc = launch_tier<SET_STAT, 256>(B, bins, kStatFallbackList, nan_from, out, ld, col0, nullptr, 0, 0, stream, dev, tk + 5, fb_grid);
-    else rc = launch_tier<SET_STAT, 512>(B, bins, kStatFallbackList, nan_from, out, ld, col0, nullptr, 0, 0, stream, dev, tk + 5, fb_grid);
+    int rc = for_tier((last < 2) ? last : 2, [&](auto cap) -> int {
+        if constexpr (cap() <= 512) return G.tier<SET_STAT, cap()>(kStatFallbackList, nan_from, stream, tk + 5, fb_grid);
+        return 0;
+    });
     if (rc) return rc;
     ++*n_launch;
     if (long_slabs && max_len > SetTraits<SET_STAT>::long_above) {
-        rc = launch_long<SET_STAT>(B, bins, 6, -1, -1, out, ld, col0, nullptr, 0, 0, stream, tk + 7, long_slabs);
+        rc = G.long_tier<SET_STAT>(6, -1, -1);
         if (rc) return rc;
         ++*n_launch;
     }
@@ -2019,6 +1843,31 @@ struct HostPathPool {
     std::mutex mutex;
 };
 HostPathPool g_pool[16];
+
+// what workspace.hpp takes from the kernels' own structures; every size a multiple of the regions' 256-byte rounding
+static_assert(kGpSmallBytes % 256 == 0 && kGpMidBytes % 256 == 0 && kGpGlobalBytes % 256 == 0 && kGp112Bytes % 256 == 0 && kGp160Bytes % 256 == 0 &&
+              kGp1dLongBytes % 256 == 0 && kGpLongBytes % 256 == 0 && kGp1dLongTierBytes % 256 == 0, "slab sizes");
+static_assert(SetTraits<SET_GP2D>::long_above == kGpGlobalNP - 1 && SetTraits<SET_GP1D>::long_above == kGpGlobalNP - 1, "last GP tier");
+const WsSizes kWsSizes = [] {
+    WsSizes z{{kGpSmallBytes, kGpMidBytes, kGpGlobalBytes, kGp112Bytes, kGp160Bytes}, kGp1dLongBytes, {}};
+    for (int s = 0; s < NUM_ALL_SETS; ++s)
+        z.long_slab[s] = for_set(s, [](auto tag) -> size_t {
+            if constexpr (tag() == SET_GP2D) return kGpLongBytes;
+            else if constexpr (tag() == SET_GP1D) return kGp1dLongTierBytes;
+            else return kLongGrid * long_slab_bytes<tag()>();
+        });
+    return z;
+}();
+
+FitWs bazin_ws(const WsLayout& L, void* ws) {
+    double* rows = (double*)L.at(ws, WS_BAZIN_ROWS);
+    return FitWs{rows, rows + L.np, rows + 2 * L.np, (int*)L.at(ws, WS_BAZIN_PBOFF), (int*)L.at(ws, WS_BAZIN_FITS), kBazinFits * (int64_t)L.no};
+}
+PlWs powerlaw_ws(const WsLayout& L, void* ws) {
+    double *rows = (double*)L.at(ws, WS_PL_ROWS), *peak = (double*)L.at(ws, WS_PL_PEAK);
+    return PlWs{rows, rows + L.np, peak, peak + kPlBands * L.no, (int*)L.at(ws, WS_PL_PBOFF), (int*)L.at(ws, WS_PL_KK),
+                (int*)L.at(ws, WS_PL_FITS_A), (int*)L.at(ws, WS_PL_FITS_B), kPlFitsA * (int64_t)L.no, kPlFitsB * (int64_t)L.no};
+}
 
 }  // namespace
 
@@ -2144,42 +1993,13 @@ const char* lcfe_colname(int mask, int64_t j) {
     return nullptr;
 }
 
-// workspace layout: [0, 1024) ticket counters (8 per set up to the extension set, then the fit lists'), [1024, 2048) bin
-// counts, [2048, 2304) ticket counters of the registered sets (8 per set), then the kNumLists index lists of n_obj int32
-// each (256-byte aligned total), then the GP scratch slabs
-constexpr size_t kWsHeader = 2304;
-static_assert((SET_ADVANCED + 1) * 8 <= kFitTicketBase && kPlTicketB + kFitTiers <= 128, "ticket counters of the first 1024 bytes");
-static_assert(kRegTicketBase * sizeof(unsigned long long) == 2048 && (kRegTicketBase + kRegTicketSets * 8) * sizeof(unsigned long long) <= kWsHeader,
-              "ticket counters of the registered sets fit the header, behind the bin counts");
-static size_t list_bytes(int64_t n_obj) {
-    return (((size_t)(n_obj > 0 ? n_obj : 0) * kNumLists * sizeof(int)) + 255) & ~(size_t)255;
-}
+// (layout: workspace.hpp)
 size_t lcfe_workspace_bytes(int mask, int64_t n_obj, int64_t n_points) {
-    size_t b = kWsHeader + list_bytes(n_obj);
-    if (mask & (1 << SET_GP2D)) b += kGpScratchBytes;
-    if (mask & (1 << SET_BAZIN)) b += bazin_ws_bytes(n_obj, n_points);
-    if (mask & (1 << SET_POWERLAW)) b += powerlaw_ws_bytes(n_obj, n_points);
-    if (mask & (1 << SET_GP1D)) b += kGp1dLongBytes;
-    return b;
+    return WsLayout(kWsSizes, mask, n_obj, n_points, 0, false).total;
 }
-
-// slabs of the long-object tier of one set (0: the set needs none for light curves of up to max_len rows)
-static size_t long_bytes_of(int set, int64_t max_len) {
-    return for_set(set, [&](auto tag) -> size_t {
-        using T = SetTraits<tag()>;
-        if (max_len <= T::long_above && T::overflow_list < 0) return 0;   // (an overflow list can fill from short light curves)
-        if constexpr (tag() == SET_GP2D) return kGpLongBytes;
-        else if constexpr (tag() == SET_GP1D) return kGp1dLongTierBytes;
-        else return kLongGrid * long_slab_bytes<tag()>();
-    });
-}
-static_assert(SetTraits<SET_GP2D>::long_above == kGpGlobalNP - 1 && SetTraits<SET_GP1D>::long_above == kGpGlobalNP - 1, "last GP tier");
 
 size_t lcfe_workspace_bytes_for(int mask, int64_t n_obj, int64_t n_points, int64_t max_len) {
-    size_t b = lcfe_workspace_bytes(mask, n_obj, n_points);
-    for (int s = 0; s < NUM_ALL_SETS; ++s)
-        if (mask & (1 << s)) b += long_bytes_of(s, max_len);
-    return b;
+    return WsLayout(kWsSizes, mask, n_obj, n_points, max_len, true).total;
 }
 
 int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int64_t n_points,
@@ -2215,35 +2035,19 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
         prof->bytes_in = 25 * n_points + 8 * (n_obj + 1) + (d_z ? 8 * n_obj : 0);
         prof->bytes_out = 8 * n_obj * (int64_t)ld;
     }
-    const size_t lists_b = list_bytes(n_obj);
-    if (!d_workspace || workspace_bytes < kWsHeader + lists_b)
+    const WsLayout L(kWsSizes, mask, n_obj, n_points, max_len, true);
+    if (!d_workspace || workspace_bytes < L.short_total)
         return fail_msg("lcfe_extract_device: workspace smaller than lcfe_workspace_bytes(mask, n_obj, n_points)");
     unsigned long long* tickets = (unsigned long long*)d_workspace;
-    int* counts = (int*)((char*)d_workspace + 1024);
-    int* lists = (int*)((char*)d_workspace + kWsHeader);
-    if (workspace_bytes < lcfe_workspace_bytes(mask, n_obj, n_points))
-        return fail_msg("lcfe_extract_device: workspace smaller than lcfe_workspace_bytes(mask, n_obj, n_points)");
-    // after the lists: the GP scratch slabs (if the 2-D GP is in the mask), then the Bazin fit workspace
-    char* region = (char*)d_workspace + kWsHeader + lists_b;
-    const size_t gp_scratch_bytes = (mask & (1 << SET_GP2D)) ? kGpScratchBytes : 0;
-    double* gp_scratch = gp_scratch_bytes ? (double*)region : nullptr;
-    region += gp_scratch_bytes;
-    void* bazin_ws = (mask & (1 << SET_BAZIN)) ? (void*)region : nullptr;
-    const size_t bazin_bytes = bazin_ws ? bazin_ws_bytes(n_obj, n_points) : 0;
-    region += bazin_bytes;
-    void* pl_ws = (mask & (1 << SET_POWERLAW)) ? (void*)region : nullptr;
-    const size_t pl_bytes = pl_ws ? powerlaw_ws_bytes(n_obj, n_points) : 0;
-    region += pl_bytes;
-    double* gp1d_slab = (mask & (1 << SET_GP1D)) ? (double*)region : nullptr;
-    if (gp1d_slab) region += kGp1dLongBytes;
+    int* counts = (int*)((char*)d_workspace + kWsCounts);
+    int* lists = (int*)L.at(d_workspace, WS_LISTS);
+    double* gp_slab[5];
+    for (int k = 0; k < 5; ++k) gp_slab[k] = (double*)L.at(d_workspace, WS_GP_SMALL + k);
     // the slabs of the long-object tier, when the workspace was sized with lcfe_workspace_bytes_for(.., max_len)
     char* long_slab[NUM_ALL_SETS] = {};
-    if (workspace_bytes >= lcfe_workspace_bytes_for(mask, n_obj, n_points, max_len)) {
-        for (int s = 0; s < NUM_ALL_SETS; ++s) {
-            const size_t lb = (mask & (1 << s)) ? long_bytes_of(s, max_len) : 0;
-            if (lb) { long_slab[s] = region; region += lb; }
-        }
-    }
+    if (workspace_bytes >= L.total)
+        for (int s = 0; s < NUM_ALL_SETS; ++s)
+            if (L.bytes[WS_LONG + s]) long_slab[s] = L.at(d_workspace, WS_LONG + s);
     const Bins bins{lists, counts, n_obj};
     // Launch plan.  The sets write disjoint columns and only read the bins, so after the shared prologue
     // (+ the statistics set, which stays alone so that its event time is a clean roofline sample) the
@@ -2264,8 +2068,7 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
     Events& E = pools[(dev >= 0 && dev < 16) ? dev : 0];
     hipEvent_t (&ev0)[NUM_ALL_SETS] = E.ev0;
     hipEvent_t (&ev1)[NUM_ALL_SETS] = E.ev1;
-    // fork / join markers are short-lived: an event that was recorded is released by the runtime once the
-    // recorded work has completed, so destroying it right after the wait was enqueued is safe
+    // (the one marker several streams wait on; every other fork and join is a stream_wait)
     struct Marker {
         hipEvent_t e = nullptr;
         ~Marker() { if (e) (void)hipEventDestroy(e); }
@@ -2303,9 +2106,9 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
         const int rc = for_set(s, [&](auto tag) -> int {
             constexpr int SET = tag();
             if constexpr (SET == SET_STAT) return A.launch_stat(fork ? side[0] : q, fork ? side[1] : q);
-            else if constexpr (SET == SET_BAZIN) return A.launch_bazin(bazin_ws, bazin_bytes, n_points);
-            else if constexpr (SET == SET_POWERLAW) return A.launch_powerlaw(pl_ws, pl_bytes, n_points);
-            else if constexpr (SET == SET_GP1D) return A.launch_gp1d(gp1d_slab);
+            else if constexpr (SET == SET_BAZIN) return A.launch_bazin(bazin_ws(L, d_workspace));
+            else if constexpr (SET == SET_POWERLAW) return A.launch_powerlaw(powerlaw_ws(L, d_workspace));
+            else if constexpr (SET == SET_GP1D) return A.launch_gp1d((double*)L.at(d_workspace, WS_GP1D));
             else if constexpr (SET == SET_GP2D) {
                 // the GP tiers, longest first, round-robin over the caller's stream and side streams 2.. (LCFE_GP_STREAMS, default
                 // 2: more streams start more tiers at once)
@@ -2319,15 +2122,9 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
                     }
                     ngs = want;
                 }
-                int rc = A.launch_gp(gs, ngs, gp_scratch, gp_scratch_bytes);
+                int rc = A.launch_gp(gs, ngs, gp_slab);
                 // the set's stop event (prof) is recorded on q: make q wait for the tiers on the other streams
-                for (int k = 1; k < ngs && !rc; ++k) {
-                    hipEvent_t half;
-                    HIP_TRY(hipEventCreateWithFlags(&half, hipEventDisableTiming));
-                    HIP_TRY(hipEventRecord(half, gs[k]));
-                    HIP_TRY(hipStreamWaitEvent(q, half, 0));
-                    (void)hipEventDestroy(half);
-                }
+                for (int k = 1; k < ngs && !rc; ++k) rc = stream_wait(q, gs[k]);
                 return rc;
             } else return A.template launch_set<SET>();
         });
@@ -2343,12 +2140,7 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
     }
     // join the side streams back into the caller's stream
     for (int k = 0; k < kSideStreams; ++k) {
-        if (!side_used[k]) continue;
-        hipEvent_t done;
-        HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(done, side[k]));
-        HIP_TRY(hipStreamWaitEvent(stream, done, 0));
-        (void)hipEventDestroy(done);       // released once the recorded work has completed
+        if (side_used[k] && stream_wait(stream, side[k])) return 1;
     }
     if (prof) {
         HIP_TRY(hipStreamSynchronize(stream));

@@ -100,3 +100,14 @@ def test_long_object_tier_templates(name):
     ref = oracle.extract(name, lc, lc["z"])
     bad = parity.compare(got, ref, COLUMNS[name], int_cols=STAT_INT_COLUMNS if name == "stat" else (), label=name, **TOL[name])
     assert not bad, "\n".join(bad)
+
+
+def test_workspace_layout_and_grid_arithmetic():
+    """csrc/workspace.hpp as a stand-alone program (tests/hostsim/workspace.cpp): every region of the workspace aligned,
+    in order, disjoint and ending at the total over the grid of test_workspace_cpu.py; grid_for against cases by hand."""
+    import os
+    import subprocess
+    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim")
+    subprocess.run(["make", "-s", "-C", d, "workspace_check"], check=True)
+    r = subprocess.run([os.path.join(d, "workspace_check")], capture_output=True, text=True)
+    assert r.returncode == 0 and "workspace OK" in r.stdout, r.stdout + r.stderr
