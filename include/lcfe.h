@@ -181,6 +181,43 @@ int lcfe_set_info(int k, int* bit, const char** name, int* ncols, int* nstatus);
  * lcfe_stats, for an extension set those of lcfe_last_ext_profile.  Returns 0, or 1 for a bit that is no set. */
 int lcfe_last_set_profile(int bit, double* kernel_ms, int32_t* launches);
 
+/*
+ * Augmentation on the device (augmentation.py:138-186, LightcurveAugmenter.augment_single): k perturbed copies of every
+ * light curve of a device-resident CSR batch, as a CSR batch of n_obj * k objects -- copy c of object i at index i * k + c --
+ * that lcfe_extract_device accepts as it is.  Like lcfe_extract_device: every pointer is a DEVICE pointer on `device`, the
+ * kernels are enqueued on `stream`, the call does not synchronise and allocates nothing.
+ *   plan         seven arrays of n_obj * k entries, entry i * k + c describes copy c of object i; the steps, in this order:
+ *     scale        flux *= scale, err *= scale
+ *     stretch      t = t_min + (t - t_min) * stretch, t_min the object's smallest time that is not NaN; 1 leaves t as it is
+ *     noise_scale  flux += err * noise_scale * N(0, 1); 0 = no noise
+ *     dropout      a fraction in [0, 1): max(5, (int64)(n * (1 - dropout))) of the object's n rows are kept, in file order;
+ *                  objects of up to 5 rows, and dropout 0, keep every row
+ *     shift        t += shift; 0 leaves t as it is
+ *     band_noise   non-zero: flux += err * {u 1.5, g 1.0, r 0.8, i 0.9, z 1.1, y 1.3} * 0.3 * N(0, 1); none for band 255
+ *     seed         key of the copy's Philox4x32-10 draws; counter (row index in the input object, stream, 0, 0) with
+ *                  stream 0 = noise, 1 = dropout keys, 2 = band noise; normals by Box-Muller on words 0 and 1,
+ *                  u = (w + 0.5) / 2^32; the rows with the smallest (word 0 << 32 | word 1, row index) are kept
+ *   add_flux     optional (NULL: none): added to the flux after the noise step; one entry per CANDIDATE row -- input row r
+ *                of copy c of object i at index k * offsets[i] + c * n_i + r
+ *   keep         optional (NULL: the Philox selection): non-zero = the candidate row is kept; replaces the dropout step
+ *   outputs      offsets_out int64[n_obj * k + 1]; t_out, flux_out, err_out float64 and band_out uint8 of at least
+ *                lcfe_augment_capacity(n_points, k) = n_points * k entries (-1: bad arguments); n_points_out int64[1], the
+ *                rows written -- or -1 when a dropout entry lies outside [0, 1): then no row is written and offsets_out is void
+ *   workspace    device scratch of at least lcfe_augment_workspace_bytes(n_obj, k) bytes (first epochs, partial sums of the
+ *                prefix sum), owned by the call until its work on `stream` has completed
+ * A light curve may have any number of rows below 2^31 (no buffer holds an object).  Errors (lcfe_last_error): k < 1, negative
+ * sizes, a NULL required array, a workspace that is too small.
+ */
+int64_t lcfe_augment_capacity(int64_t n_points, int k);
+size_t lcfe_augment_workspace_bytes(int64_t n_obj, int k);
+int lcfe_augment_device(int device, void* stream, int64_t n_obj, int64_t n_points, int k, const int64_t* d_offsets,
+                        const double* d_t, const double* d_flux, const double* d_err, const uint8_t* d_band,
+                        const double* d_scale, const double* d_stretch, const double* d_shift, const double* d_noise_scale,
+                        const double* d_dropout, const uint8_t* d_band_noise, const uint64_t* d_seed,
+                        const double* d_add_flux, const uint8_t* d_keep, int64_t* d_offsets_out, double* d_t_out,
+                        double* d_flux_out, double* d_err_out, uint8_t* d_band_out, int64_t* d_n_points_out,
+                        void* d_workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

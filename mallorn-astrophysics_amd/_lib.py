@@ -104,6 +104,13 @@ def load():
     lib.lcfe_extract_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                         ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 9 + \
                                        [ctypes.c_size_t, ctypes.POINTER(LcfeStats)]
+    lib.lcfe_augment_capacity.restype = ctypes.c_int64
+    lib.lcfe_augment_capacity.argtypes = [ctypes.c_int64, ctypes.c_int]
+    lib.lcfe_augment_workspace_bytes.restype = ctypes.c_size_t
+    lib.lcfe_augment_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int]
+    lib.lcfe_augment_device.restype = ctypes.c_int
+    lib.lcfe_augment_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + \
+                                       [ctypes.c_void_p] * 21 + [ctypes.c_size_t]
     _lib = lib
     return lib
 

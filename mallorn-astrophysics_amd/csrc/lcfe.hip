@@ -22,6 +22,7 @@
 #include "stat_lanes.hpp"
 #include "stat_lanes16.hpp"
 #include "gp1d.hpp"
+#include "augment.hpp"
 
 using namespace lcfe;
 
@@ -1869,6 +1870,101 @@ PlWs powerlaw_ws(const WsLayout& L, void* ws) {
                 (int*)L.at(ws, WS_PL_FITS_A), (int*)L.at(ws, WS_PL_FITS_B), kPlFitsA * (int64_t)L.no, kPlFitsB * (int64_t)L.no};
 }
 
+// ---- augmentation (augment.hpp): count, prefix sum in place, write.  One wavefront per INPUT object -- its first epoch is
+// found once for the k copies -- and kAugWaves objects per workgroup; the grids stride over the objects.
+constexpr int kAugWaves = 4;
+constexpr int kAugScanThreads = 256, kAugScanItems = 8, kAugScanTile = kAugScanThreads * kAugScanItems;
+// workspace: [0, 256) the bad-plan flag, then the first epochs double[n_obj], then one partial sum per scan tile
+constexpr size_t kAugWsHeader = 256;
+struct AugWs {
+    int* flag;
+    double* tmin;
+    int64_t* tile_sum;
+    int64_t tiles;
+    size_t bytes;
+    AugWs(void* ws, int64_t n_obj, int k) {
+        tiles = (n_obj * k + kAugScanTile - 1) / kAugScanTile;
+        const size_t tmin_bytes = ((size_t)n_obj * 8 + 255) & ~(size_t)255;
+        flag = (int*)ws;
+        tmin = (double*)((char*)ws + kAugWsHeader);
+        tile_sum = (int64_t*)((char*)ws + kAugWsHeader + tmin_bytes);
+        bytes = kAugWsHeader + tmin_bytes + (((size_t)tiles * 8 + 255) & ~(size_t)255);
+    }
+};
+
+__global__ __launch_bounds__(64 * kAugWaves) void augment_count_kernel(AugIn A, AugPlan P, int64_t n_obj, double* tmin, int64_t* offsets_out,
+                                                                        int* flag) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) offsets_out[0] = 0;
+    const int64_t stride = (int64_t)gridDim.x * kAugWaves;
+    for (int64_t i = (int64_t)blockIdx.x * kAugWaves + (threadIdx.x >> 6); i < n_obj; i += stride)
+        if (!aug_count_object<AugWave>(A, P, i, tmin, offsets_out + 1) && AugWave::lane() == 0) atomicOr(flag, 1);
+}
+
+// sum of the workgroup's values v (one per thread) below each thread, and their total: Hillis-Steele over LDS
+__device__ __forceinline__ int64_t aug_block_exclusive(int64_t v, int64_t* total) {
+    __shared__ int64_t buf[2][kAugScanThreads];
+    const int tid = threadIdx.x;
+    int cur = 0;
+    buf[0][tid] = v;
+    __syncthreads();
+    for (int d = 1; d < kAugScanThreads; d <<= 1) {
+        buf[cur ^ 1][tid] = buf[cur][tid] + ((tid >= d) ? buf[cur][tid - d] : 0);
+        cur ^= 1;
+        __syncthreads();
+    }
+    const int64_t incl = buf[cur][tid];
+    *total = buf[cur][kAugScanThreads - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+// x[0..m) in tiles of kAugScanTile entries: the sum of every tile ...
+__global__ __launch_bounds__(kAugScanThreads) void augment_scan_tiles_kernel(const int64_t* x, int64_t m, int64_t* tile_sum) {
+    const int64_t base = (int64_t)blockIdx.x * kAugScanTile + (int64_t)threadIdx.x * kAugScanItems;
+    int64_t s = 0;
+#pragma unroll
+    for (int j = 0; j < kAugScanItems; ++j) s += (base + j < m) ? x[base + j] : 0;
+    int64_t total;
+    aug_block_exclusive(s, &total);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+// ... the tile sums into the sums of the tiles before each (one workgroup), and the grand total -- -1 for a bad plan ...
+__global__ __launch_bounds__(kAugScanThreads) void augment_scan_sums_kernel(int64_t* tile_sum, int64_t tiles, const int* flag, int64_t* n_points_out) {
+    int64_t carry = 0;
+    for (int64_t base = 0; base < tiles; base += kAugScanThreads) {
+        const int64_t j = base + threadIdx.x;
+        const int64_t v = (j < tiles) ? tile_sum[j] : 0;
+        int64_t total;
+        const int64_t ex = aug_block_exclusive(v, &total);
+        if (j < tiles) tile_sum[j] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) *n_points_out = *flag ? -1 : carry;
+}
+// ... and every entry replaced by the sum of the entries up to and including it
+__global__ __launch_bounds__(kAugScanThreads) void augment_scan_apply_kernel(int64_t* x, int64_t m, const int64_t* tile_sum) {
+    const int64_t base = (int64_t)blockIdx.x * kAugScanTile + (int64_t)threadIdx.x * kAugScanItems;
+    int64_t v[kAugScanItems], s = 0;
+#pragma unroll
+    for (int j = 0; j < kAugScanItems; ++j) { v[j] = (base + j < m) ? x[base + j] : 0; s += v[j]; }
+    int64_t total;
+    int64_t run = tile_sum[blockIdx.x] + aug_block_exclusive(s, &total);
+#pragma unroll
+    for (int j = 0; j < kAugScanItems; ++j) {
+        run += v[j];
+        if (base + j < m) x[base + j] = run;
+    }
+}
+
+__global__ __launch_bounds__(64 * kAugWaves) void augment_write_kernel(AugIn A, AugPlan P, AugOut O, int64_t n_obj, const double* tmin,
+                                                                        const int* flag) {
+    __shared__ int hist[kAugWaves][64];
+    if (*flag) return;                       // a bad plan: the counts are void, nothing is written
+    const int64_t stride = (int64_t)gridDim.x * kAugWaves;
+    for (int64_t i = (int64_t)blockIdx.x * kAugWaves + (threadIdx.x >> 6); i < n_obj; i += stride)
+        aug_write_object<AugWave>(A, P, O, i, tmin, hist[threadIdx.x >> 6]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2249,6 +2345,64 @@ void lcfe_release_buffers(void) {
         if (guard.enter(d)) continue;
         for (int k = 0; k < HostPathPool::NBUF; ++k) { if (P.buf[k]) (void)hipFree(P.buf[k]); P.buf[k] = nullptr; P.cap[k] = 0; }
     }
+}
+
+int64_t lcfe_augment_capacity(int64_t n_points, int k) {
+    if (n_points < 0 || k < 1 || n_points > INT64_MAX / k) return -1;
+    return n_points * k;
+}
+
+size_t lcfe_augment_workspace_bytes(int64_t n_obj, int k) {
+    if (n_obj < 0 || k < 1 || n_obj > (INT64_MAX >> 4) / k) return 0;
+    return AugWs(nullptr, n_obj, k).bytes;
+}
+
+int lcfe_augment_device(int device, void* stream_, int64_t n_obj, int64_t n_points, int k, const int64_t* d_offsets,
+                        const double* d_t, const double* d_flux, const double* d_err, const uint8_t* d_band, const double* d_scale,
+                        const double* d_stretch, const double* d_shift, const double* d_noise_scale, const double* d_dropout,
+                        const uint8_t* d_band_noise, const uint64_t* d_seed, const double* d_add_flux, const uint8_t* d_keep,
+                        int64_t* d_offsets_out, double* d_t_out, double* d_flux_out, double* d_err_out, uint8_t* d_band_out,
+                        int64_t* d_n_points_out, void* d_workspace, size_t workspace_bytes) {
+    g_err.clear();
+    if (k < 1) return fail_msg("lcfe_augment_device: k must be at least 1");
+    if (n_obj < 0 || n_points < 0) return fail_msg("lcfe_augment_device: negative size");
+    if (lcfe_augment_capacity(n_points, k) < 0 || n_obj > (INT64_MAX >> 4) / k) return fail_msg("lcfe_augment_device: n_points * k or n_obj * k overflows");
+    if (!d_offsets || !d_offsets_out || !d_n_points_out) return fail_msg("lcfe_augment_device: null offsets or n_points_out");
+    if (n_obj > 0 && (!d_scale || !d_stretch || !d_shift || !d_noise_scale || !d_dropout || !d_band_noise || !d_seed))
+        return fail_msg("lcfe_augment_device: null plan array");
+    if (n_points > 0 && (!d_t || !d_flux || !d_err || !d_band || !d_t_out || !d_flux_out || !d_err_out || !d_band_out))
+        return fail_msg("lcfe_augment_device: null sample array");
+    const AugWs W(d_workspace, n_obj, k);
+    if (!d_workspace || workspace_bytes < W.bytes) return fail_msg("lcfe_augment_device: workspace smaller than lcfe_augment_workspace_bytes(n_obj, k)");
+    if (W.tiles > 0x7fffffff) return fail_msg("lcfe_augment_device: more than 2^42 output objects");
+    DeviceGuard guard;
+    if (guard.enter(device)) return fail_msg("lcfe_augment_device: cannot select device " + std::to_string(device));
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipMemsetAsync(d_workspace, 0, kAugWsHeader, stream));
+    if (n_obj == 0) {
+        HIP_TRY(hipMemsetAsync(d_offsets_out, 0, sizeof(int64_t), stream));
+        HIP_TRY(hipMemsetAsync(d_n_points_out, 0, sizeof(int64_t), stream));
+        return 0;
+    }
+    const AugIn A{d_offsets, d_t, d_flux, d_err, d_band, d_add_flux, d_keep, k};
+    const AugPlan P{d_scale, d_stretch, d_shift, d_noise_scale, d_dropout, d_band_noise, d_seed};
+    const AugOut O{d_offsets_out, d_t_out, d_flux_out, d_err_out, d_band_out};
+    const int64_t groups = (n_obj + kAugWaves - 1) / kAugWaves, cap = (int64_t)num_cus(dev) * 8;
+    const unsigned grid = (unsigned)((groups < cap) ? groups : cap);
+    const int64_t m = n_obj * k;
+    hipLaunchKernelGGL(augment_count_kernel, dim3(grid), dim3(64 * kAugWaves), 0, stream, A, P, n_obj, W.tmin, d_offsets_out, W.flag);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(augment_scan_tiles_kernel, dim3((unsigned)W.tiles), dim3(kAugScanThreads), 0, stream, d_offsets_out + 1, m, W.tile_sum);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(augment_scan_sums_kernel, dim3(1), dim3(kAugScanThreads), 0, stream, W.tile_sum, W.tiles, W.flag, d_n_points_out);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(augment_scan_apply_kernel, dim3((unsigned)W.tiles), dim3(kAugScanThreads), 0, stream, d_offsets_out + 1, m, W.tile_sum);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(augment_write_kernel, dim3(grid), dim3(64 * kAugWaves), 0, stream, A, P, O, n_obj, W.tmin, W.flag);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 }  // extern "C"

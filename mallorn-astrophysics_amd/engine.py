@@ -148,3 +148,54 @@ class DeviceBatch:
         if prof:
             return out, status, _profile(st, mask)
         return out, status
+
+    def augment(self, plan, add_flux=None, keep=None):
+        """``plan.n_copies`` perturbed copies of every object (``augment.AugmentPlan``) as a new batch on the same device:
+        copy ``c`` of object ``i`` is object ``i * n_copies + c`` of the result, its redshift that of object ``i``.
+
+        Explicit mode: ``add_flux`` float64 and ``keep`` uint8, host arrays over the ``n_copies * n_points`` candidate rows
+        (input row ``r`` of copy ``c`` of object ``i`` at ``n_copies * offsets[i] + c * n_i + r``): ``add_flux`` is added to
+        the flux after the noise step, ``keep`` replaces the dropout selection."""
+        torch = self.torch
+        lib = _lib.load()
+        k = plan.n_copies
+        if plan.n_obj != self.n_obj:
+            raise ValueError(f"the plan is for {plan.n_obj} objects, the batch has {self.n_obj}")
+        cap = int(lib.lcfe_augment_capacity(self.n_points, k))
+        if cap < 0:
+            raise ValueError("n_points * n_copies overflows")
+        to = lambda a: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(self.device)
+        fields = [to(a) for a in plan.arrays().values()]
+
+        def explicit(a, dt, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dt)
+            if a.shape != (cap,):                   # a short array would be read out of bounds on the device
+                raise ValueError(f"{name} must have n_copies * n_points = {cap} entries")
+            return to(a)
+
+        d_add, d_keep = explicit(add_flux, np.float64, "add_flux"), explicit(keep, np.uint8, "keep")
+        new = object.__new__(DeviceBatch)
+        new.torch, new.device, new._ws = torch, self.device, None
+        new.n_obj = self.n_obj * k
+        empty = lambda n, dt: torch.empty(max(int(n), 1), dtype=dt, device=self.device)
+        new.offsets = empty(new.n_obj + 1, torch.int64)
+        t, flux, err, band = [empty(cap, torch.float64) for _ in range(3)] + [empty(cap, torch.uint8)]
+        total = empty(1, torch.int64)
+        wsb = int(lib.lcfe_augment_workspace_bytes(self.n_obj, k))
+        ws = empty(wsb, torch.uint8)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
+        rc = lib.lcfe_augment_device(self.device.index, ctypes.c_void_p(stream), self.n_obj, self.n_points, k, p(self.offsets),
+                                     p(self.t), p(self.flux), p(self.err), p(self.band), *[p(a) for a in fields], p(d_add),
+                                     p(d_keep), p(new.offsets), p(t), p(flux), p(err), p(band), p(total), p(ws), wsb)
+        _lib.check(rc, "lcfe_augment_device")
+        new.n_points = int(total.item())            # waits for the kernels: the row count sizes the views below
+        if new.n_points < 0:
+            raise _lib.LcfeError("lcfe_augment_device: a dropout fraction of the plan lies outside [0, 1)")
+        new.offsets = new.offsets[:new.n_obj + 1]
+        new.t, new.flux, new.err, new.band = t[:new.n_points], flux[:new.n_points], err[:new.n_points], band[:new.n_points]
+        new.z = None if self.z is None else self.z.repeat_interleave(k)
+        new.max_len = int(torch.diff(new.offsets).max().item()) if new.n_obj else 0
+        return new
