@@ -20,7 +20,6 @@
 #include "workspace.hpp"
 #include "stat_lean.hpp"
 #include "stat_lanes.hpp"
-#include "stat_lanes16.hpp"
 #include "gp1d.hpp"
 #include "augment.hpp"
 
@@ -407,22 +406,61 @@ int SetLaunch::long_tier(int l0, int l1, int l2) const {
     return 0;
 }
 
-// Statistics, eight light curves per wavefront and one lane per band (stat_lanes.hpp: CAP = rows of u, g, z, y a lane
-// holds -- r and i: 2 CAP over two lanes; ITERS = rows / 8 of the light curve).  One workgroup = one batch of eight
-// consecutive entries of one of the lists the plan kernels fill: 32-row lanes for light curves of up to 256 rows, 32-
-// and 16-row lanes for those of up to 128 rows -- or one batch of FOUR entries of the two lists of light curves with
-// longer bands (stat_lanes16.hpp: 16 lanes per light curve, up to 256 resp. 512 rows).  The lists' lengths are known
-// on the device only; the grid covers n_obj / 4 + 6 batches and the workgroups behind the last batch leave at once.  A light curve whose rows turn
-// out not to ascend in time is appended to list `retry`.
+// Statistics, several light curves per wavefront and the bands in lanes of their own (stat_lanes.hpp: LPO = lanes per
+// light curve, CAP = rows a lane holds -- a band of P parts has up to P x CAP, ITERS = rows / LPO of the light curve).
+// One workgroup = one batch of 64 / LPO consecutive entries of one of the lists stat_plan_kernel fills; the routes are
+// served in the table's order, the long batches first: they are the ones whose tail would otherwise stick out.
+struct StatLanesRoute {
+    int list, lpo, cap, iters;
+    constexpr int batch() const { return 64 / lpo; }       // light curves per workgroup
+    constexpr int rows() const { return lpo * iters; }      // rows of a light curve
+    // what stat_plan_kernel calls `eff`: the rows of u a lane group takes (r and i twice that, g, z, y the same: asserted below)
+    constexpr int eff() const { return (lpo == 8) ? lanes_capacity<LanesLayout<8>>(0, cap) : lanes_capacity<LanesLayout<16>>(0, cap); }
+};
+constexpr int kStatLanesRoutes = 5;
+constexpr StatLanesRoute kStatLanesRoute[kStatLanesRoutes] = {
+    {kStatW32List, 16, 32, 32}, {kStatW16List, 16, 32, 16}, {kStatL32xList, 8, 32, 32}, {kStatL32List, 8, 32, 16}, {kStatL16List, 8, 16, 16}};
+template <class L>
+constexpr bool lanes_eff_proportions() {
+    for (int b = 0; b < kLanesBands; ++b)
+        if (L::parts(b) != ((b == 2 || b == 3) ? 2 : 1) * L::parts(0)) return false;
+    return true;
+}
+static_assert(lanes_eff_proportions<LanesLayout<8>>() && lanes_eff_proportions<LanesLayout<16>>(), "r and i take twice the rows of the other bands");
+constexpr int kStatLanesMaxCap = 32;                        // the LDS buffer of the kernel
+// does the kernel behind `list` take every light curve of up to n rows whose bands need up to `eff` rows per lane of 8?
+constexpr bool stat_route_takes(int list, int n, int eff) {
+    for (int r = 0; r < kStatLanesRoutes; ++r)
+        if (kStatLanesRoute[r].list == list)
+            return kStatLanesRoute[r].cap <= kStatLanesMaxCap && n <= kStatLanesRoute[r].rows() && eff <= kStatLanesRoute[r].eff();
+    return false;
+}
+// The lists' lengths are known on the device only; the grid covers n_obj / 4 + 6 batches and the workgroups behind the
+// last batch leave at once.  A light curve whose rows turn out not to ascend in time is appended to list `retry`.
+// Batch `b`, numbered from route R's first: route R's if its list has that many batches, else the next route's.
+template <int R>
+__device__ __forceinline__ void stat_lanes_route(int b, const int (&count)[kStatLanesRoutes], const BatchView& B, const Bins& bins, LanesBuf lbuf,
+                                                 LanesBuf lall, double* out, int ld, int col0, int* rl, int* rc) {
+    if constexpr (R < kStatLanesRoutes) {
+        constexpr StatLanesRoute r = kStatLanesRoute[R];
+        const int nb = (count[R] + r.batch() - 1) / r.batch();
+        if (b < nb) {
+            stat_lanes_run<r.lpo, r.cap, r.iters>(B.offsets, B.t, B.f, B.e, B.b, bins.lists + (int64_t)r.list * bins.stride, count[R], b, lbuf,
+                                                  lall, out, ld, col0, rl, rc);
+            return;
+        }
+        stat_lanes_route<R + 1>(b - nb, count, B, bins, lbuf, lall, out, ld, col0, rl, rc);
+    }
+}
 #ifdef LCFE_DEBUG
 constexpr double kLanesCanary = 0x1.5ca1ab1edeadp+900;
 #endif
 __global__ __launch_bounds__(64, 2) void stat_lanes_all_kernel(BatchView B, Bins bins, int retry, double* out, int ld, int col0) {
 #ifdef LCFE_DEBUG
     // debug build: canary words around the buffers, verified when the workgroup's batch is done
-    struct Framed { double pre[8]; StatLanesLds<32> L; double post[8]; };
+    struct Framed { double pre[8]; StatLanesLds<kStatLanesMaxCap> L; double post[8]; };
     __shared__ Framed F;
-    StatLanesLds<32>& L = F.L;
+    StatLanesLds<kStatLanesMaxCap>& L = F.L;
     if (threadIdx.x < 8) { F.pre[threadIdx.x] = kLanesCanary; F.post[threadIdx.x] = kLanesCanary; }
     __syncthreads();
     unsigned int lanes_bad[2] = {0u, 0u};
@@ -437,38 +475,16 @@ __global__ __launch_bounds__(64, 2) void stat_lanes_all_kernel(BatchView B, Bins
     } canary_check{F, lanes_bad};
     unsigned int* const bad_p = lanes_bad;
 #else
-    __shared__ StatLanesLds<32> L;
+    __shared__ StatLanesLds<kStatLanesMaxCap> L;
     unsigned int* const bad_p = nullptr;
 #endif
-    const LanesBuf lbuf = lanes_buf(L.buf, 64 * StatLanesLds<32>::STRIDE, bad_p), lall = lanes_buf(L.all_rows, 8 * 17, bad_p);
-    const int c16 = bins.counts[kStatL16List], c32 = bins.counts[kStatL32List], c32x = bins.counts[kStatL32xList];
-    const int cw16 = bins.counts[kStatW16List], cw32 = bins.counts[kStatW32List];
-    const int nb16 = (c16 + 7) >> 3, nb32 = (c32 + 7) >> 3, nb32x = (c32x + 7) >> 3, nbw16 = (cw16 + 3) >> 2, nbw32 = (cw32 + 3) >> 2;
-    int b = (int)blockIdx.x;
-    int* rl = bins.lists + (int64_t)retry * bins.stride;
-    int* rc = &bins.counts[retry];
-    // (the long batches first: they are the ones whose tail would otherwise stick out)
-    if (b < nbw32) {
-        stat_lanes16_run<32, 32>(B.offsets, B.t, B.f, B.e, B.b, bins.lists + (int64_t)kStatW32List * bins.stride, cw32, b, lbuf,
-                                 lall, out, ld, col0, rl, rc);
-        return;
-    }
-    b -= nbw32;
-    if (b < nbw16) {
-        stat_lanes16_run<32, 16>(B.offsets, B.t, B.f, B.e, B.b, bins.lists + (int64_t)kStatW16List * bins.stride, cw16, b, lbuf,
-                                 lall, out, ld, col0, rl, rc);
-        return;
-    }
-    b -= nbw16;
-    if (b < nb32x)
-        stat_lanes_run<32, 32>(B.offsets, B.t, B.f, B.e, B.b, bins.lists + (int64_t)kStatL32xList * bins.stride, c32x, b, lbuf, lall, out, ld,
-                               col0, rl, rc);
-    else if (b < nb32x + nb32)
-        stat_lanes_run<32, 16>(B.offsets, B.t, B.f, B.e, B.b, bins.lists + (int64_t)kStatL32List * bins.stride, c32, b - nb32x, lbuf, lall, out,
-                               ld, col0, rl, rc);
-    else if (b < nb32x + nb32 + nb16)
-        stat_lanes_run<16, 16>(B.offsets, B.t, B.f, B.e, B.b, bins.lists + (int64_t)kStatL16List * bins.stride, c16, b - nb32x - nb32, lbuf,
-                               lall, out, ld, col0, rl, rc);
+    const LanesBuf lbuf = lanes_buf(L.buf, 64 * StatLanesLds<kStatLanesMaxCap>::STRIDE, bad_p), lall = lanes_buf(L.all_rows, 8 * 17, bad_p);
+    static_assert(kStatLanesRoutes == 5, "one count per route");
+    const int count[kStatLanesRoutes] = {bins.counts[kStatLanesRoute[0].list], bins.counts[kStatLanesRoute[1].list],
+                                         bins.counts[kStatLanesRoute[2].list], bins.counts[kStatLanesRoute[3].list],
+                                         bins.counts[kStatLanesRoute[4].list]};
+    stat_lanes_route<0>((int)blockIdx.x, count, B, bins, lbuf, lall, out, ld, col0, bins.lists + (int64_t)retry * bins.stride,
+                        &bins.counts[retry]);
 }
 
 // Which statistics kernel takes a light curve of up to 512 rows: ONE launch over the three tier lists (128 / 256 / 512
@@ -484,6 +500,13 @@ __global__ __launch_bounds__(64, 2) void stat_lanes_all_kernel(BatchView B, Bins
 // takes 128 consecutive entries of one tier list (the long tier first); the lists' lengths are known on the device only,
 // so the grid covers n_obj / 128 + 3 workgroups and the ones behind the last slice leave at once.  Lists are appended
 // per workgroup with one atomic per destination.
+// (stat_plan_kernel's thresholds, written once more here and held against the route table and the lanes layouts: a
+//  route or layout that no longer takes what the plan sends it fails the build.  The kernel below has literals of its
+//  own, which nothing ties to these: whoever edits them edits this list with them -- else a light curve reaches a list
+//  whose kernel can only send it on to the retry list.)
+static_assert(stat_route_takes(kStatL16List, 128, 16) && stat_route_takes(kStatL32List, 128, 32) && stat_route_takes(kStatW16List, 128, 64) &&
+                  stat_route_takes(kStatL32xList, 256, 32) && stat_route_takes(kStatW16List, 256, 64) && stat_route_takes(kStatW32List, 512, 64),
+              "stat_plan_kernel's thresholds (eff <= 16 / 32 / 64, n <= 128 / 256 / 512) and kStatLanesRoute");
 constexpr int kPlanThreads = 1024;
 constexpr int kPlanDst = 6;
 template <int ITERS>

@@ -1,31 +1,39 @@
-// stat_lanes.hpp -- statistics with EIGHT light curves per wavefront and one lane per band.
+// stat_lanes.hpp -- statistics with SEVERAL light curves per wavefront and the bands in lanes of their own.
 //
 // The one-object-per-wavefront kernels (stat_lean.hpp) spend most of their instructions on things that
 // are not statistics: cross-lane partner fetches of the sorting networks, 15 DPP reductions per group,
-// padding of 23-row bands to 32 slots in 8 of 64 lanes.  Here a light curve owns an 8-lane group and a
-// BAND OWNS A LANE: the band's fluxes sit in that lane's registers, the moment passes are plain serial
+// padding of 23-row bands to 32 slots in 8 of 64 lanes.  Here a light curve owns a group of LPO lanes and a
+// BAND OWNS ITS LANES: the band's fluxes sit in those lanes' registers, the moment passes are plain serial
 // loops without any reduction, the band sort is a sorting network on registers (v_min/v_max pairs, no
-// partner fetch) and eight light curves share every instruction.  r and i, the two long bands of the
-// survey's cadence, are split in time over two lanes each, so that a register array of CAP values
-// holds bands of CAP rows (u, g, z, y) and 2 CAP rows (r, i):
+// partner fetch) and all light curves of the wavefront share every instruction.  A band is split in time over
+// its lanes (its "parts"), r and i -- the two long bands of the survey's cadence -- over twice as many as the
+// others, so that a register array of CAP values holds bands of parts x CAP rows.  The two layouts
+// (LanesLayout<LPO>):
 //
+//   LPO = 8, eight light curves per wavefront: u, g, z, y one lane (CAP rows), r and i two (2 CAP rows)
 //     lane of the group   0   1   2        3         4   5   6        7
 //     rows                u   g   r first  r second  z   y   i first  i second
 //
-// One workgroup (= one wavefront) takes one batch of eight light curves; lane j of a group first holds rows j, j + 8,
-// ... of its light curve (t, f, e, band code) in registers from ONE round of loads.  Phases (one LDS buffer of
+//   LPO = 16, four light curves per wavefront: u, g, z, y two lanes (2 CAP rows), r and i four (4 CAP rows) -- a lane
+//   takes 1/16 of the rows, so light curves of up to 512 rows keep the register and LDS footprint of LPO = 8 at 256
+//     lane of the group   0  1   2  3   4  5  6  7   8  9   10 11   12 13 14 15
+//     rows                u  u   g  g   r  r  r  r   z  z   y  y    i  i  i  i
+//
+// One workgroup (= one wavefront) takes one batch of 64 / LPO light curves; lane j of a group first holds rows j,
+// j + LPO, ... of its light curve (t, f, e, band code) in registers from ONE round of loads.  Phases (one LDS buffer of
 // 64 columns x (CAP + 1) doubles per wavefront, reused):
-//   A  positions: a row's slot = number of earlier rows of its band (ballots over the 8 rows of a trip); per row also
+//   A  positions: a row's slot = number of earlier rows of its band (ballots over the LPO rows of a trip); per row also
 //      the all-rows slope and the "rows ascend in time" check from the file-order neighbours (next lane / next trip)
 //      and the SNR term |f| / e
-//   F  fluxes -> LDS (column = lane that owns the band half) -> registers v[0..CAP); sums, NaN flags
+//   F  fluxes -> LDS (column = lane that owns the part of the band) -> registers v[0..CAP); sums, NaN flags
 //   T  times  -> LDS -> band slopes against the register-resident fluxes
 //   Q  SNR terms -> LDS -> sums
 //   then the two centred passes (band and all-rows moments side by side, select-free on a copy padded with the band
-//   mean; the all-rows sums are the 8-lane sums of the lanes' partials), the register sort, and the all-rows order
-//   statistics from a bitonic MERGE of the eight sorted lanes (whose first level is the merge of the r and i halves).
-//   Extrema and order statistics are read off LDS dumps of the sorted registers by one lane per sequence; the
-//   all-rows columns are parked in LDS as they get ready (the kernel has no register to spare: 256 per lane, no spill).
+//   mean; a band's sums are combined over its lanes, the all-rows sums over the group), the register sort, and a
+//   bitonic MERGE of the sorted lanes, level by level: a band of P parts is complete after log2(P) levels, the light
+//   curve after log2(LPO).  Extrema and order statistics are read off the LDS dump of the level that completes their
+//   sequence by one lane per sequence; the all-rows columns are parked in LDS as they get ready (the kernel has no
+//   register to spare).
 // Which light curves come here is decided by stat_plan_kernel (lcfe.hip) from the rows per band; a light curve whose
 // rows turn out not to ascend in time is appended to the general kernel's list.  Same arithmetic per element as
 // stat.hpp (two-pass moments, exact counts, numpy's percentile interpolation, exact MAD); the sums are associated
@@ -56,6 +64,137 @@ struct OddEvenNet {
 };
 template <int N>
 inline constexpr OddEvenNet<N> kOddEvenNet{};
+
+}  // namespace lcfe
+
+#if defined(__HIPCC__)
+namespace lcfe {
+// reductions over the 16 lanes of a DPP row (= one light curve's group): every lane gets the result
+struct Lanes16 {
+    template <class V, class Op>
+    static __device__ __forceinline__ V reduce(V v, Op op) {
+        v = op(v, WaveDev::dpp<0xB1>(v));      // quad_perm(1,0,3,2)
+        v = op(v, WaveDev::dpp<0x4E>(v));      // quad_perm(2,3,0,1)
+        v = op(v, WaveDev::dpp<0x141>(v));     // row_half_mirror
+        v = op(v, WaveDev::dpp<0x140>(v));     // row_mirror
+        return v;
+    }
+    static __device__ __forceinline__ double sum(double v) { return reduce(v, [](double a, double b) { return a + b; }); }
+    static __device__ __forceinline__ double max(double v) { return reduce(v, [](double a, double b) { return (b > a) ? b : a; }); }
+    static __device__ __forceinline__ double min(double v) { return reduce(v, [](double a, double b) { return (b < a) ? b : a; }); }
+    static __device__ __forceinline__ int sum(int v) { return reduce(v, [](int a, int b) { return a + b; }); }
+    static __device__ __forceinline__ int max(int v) { return reduce(v, [](int a, int b) { return (b > a) ? b : a; }); }
+    static __device__ __forceinline__ int min(int v) { return reduce(v, [](int a, int b) { return (b < a) ? b : a; }); }
+    static __device__ __forceinline__ bool any(bool p) { return max(p ? 1 : 0) != 0; }
+    static __device__ __forceinline__ bool all(bool p) { return min(p ? 1 : 0) != 0; }
+    static __device__ __forceinline__ void sync() { GroupDev<8>::sync(); }
+};
+}  // namespace lcfe
+#endif
+
+namespace lcfe {
+
+// ---- who holds what: LPO lanes per light curve.  band_of / first_lane / parts are the lane -> band table, the band ->
+// first-lane table and the lanes ("parts", a power of two) a band is split over in time; G the reductions over the
+// group; WRAP_DPP the DPP control with which the last lane of a group reads the first (the file-order neighbour of its
+// row is in the next trip); ALL_ROWS_LANE the lane that writes the all-rows columns -- one that reads no band's order
+// statistics.  A 32-lane layout would be a third specialisation (and reductions over two DPP rows).
+constexpr int kLanesBands = 6;
+template <int LANES_PER_OBJECT>
+struct LanesLayout;
+template <>
+struct LanesLayout<8> {
+    static constexpr int LPO = 8, MAX_PARTS = 2, ALL_ROWS_LANE = 3, WRAP_DPP = 0x117;        // row_shr:7
+    static constexpr int band_of(int lane) { constexpr int t[LPO] = {0, 1, 2, 2, 4, 5, 3, 3}; return t[lane]; }
+    static constexpr int first_lane(int band) { constexpr int t[kLanesBands] = {0, 1, 2, 6, 4, 5}; return t[band]; }
+    static constexpr int parts(int band) { constexpr int t[kLanesBands] = {1, 1, 2, 2, 1, 1}; return t[band]; }
+#if defined(__HIPCC__)
+    using G = GroupDev<8>;
+#endif
+};
+template <>
+struct LanesLayout<16> {
+    static constexpr int LPO = 16, MAX_PARTS = 4, ALL_ROWS_LANE = 1, WRAP_DPP = 0x11F;       // row_shr:15
+    static constexpr int band_of(int lane) { constexpr int t[LPO] = {0, 0, 1, 1, 2, 2, 2, 2, 4, 4, 5, 5, 3, 3, 3, 3}; return t[lane]; }
+    static constexpr int first_lane(int band) { constexpr int t[kLanesBands] = {0, 2, 4, 12, 8, 10}; return t[band]; }
+    static constexpr int parts(int band) { constexpr int t[kLanesBands] = {2, 2, 4, 4, 2, 2}; return t[band]; }
+#if defined(__HIPCC__)
+    using G = Lanes16;
+#endif
+};
+
+// the part of its band a lane holds
+template <class L>
+constexpr int lanes_part_of(int lane) { return lane - L::first_lane(L::band_of(lane)); }
+// The two tables are inverse to each other: a band's lanes are first_lane .. first_lane + parts - 1, an aligned block of
+// 2^k lanes (the merge levels pair aligned blocks), and no lane is left over.
+template <class L>
+constexpr bool lanes_tables_inverse() {
+    for (int b = 0; b < kLanesBands; ++b) {
+        const int p = L::parts(b), f = L::first_lane(b);
+        if (p < 1 || p > L::MAX_PARTS || (p & (p - 1)) != 0 || f % p != 0 || f + p > L::LPO) return false;
+        for (int q = 0; q < p; ++q)
+            if (L::band_of(f + q) != b) return false;
+    }
+    for (int l = 0; l < L::LPO; ++l) {
+        const int b = L::band_of(l);
+        if (b < 0 || b >= kLanesBands || lanes_part_of<L>(l) < 0 || lanes_part_of<L>(l) >= L::parts(b)) return false;
+    }
+    return lanes_part_of<L>(L::ALL_ROWS_LANE) != 0;
+}
+template <class L>
+constexpr int lanes_parts_total() {
+    int total = 0;
+    for (int b = 0; b < kLanesBands; ++b) total += L::parts(b);
+    return total;
+}
+static_assert(lanes_tables_inverse<LanesLayout<8>>() && lanes_tables_inverse<LanesLayout<16>>(), "lane -> band and band -> first lane");
+static_assert(lanes_parts_total<LanesLayout<8>>() == 8 && lanes_parts_total<LanesLayout<16>>() == 16, "the parts fill the group");
+
+// ---- the index arithmetic of the kernels (plain functions: tests/test_stat_lanes_layout.py runs them on the CPU)
+// rows a band may have when a lane holds `cap`
+template <class L>
+constexpr int lanes_capacity(int band, int cap) { return L::parts(band) * cap; }
+// a band of `count` rows is taken (the kernel sends the light curve of one that is not to the retry list)
+template <class L>
+constexpr bool lanes_band_fits(int band, int count, int cap) { return count <= lanes_capacity<L>(band, cap); }
+// merge levels after which the band's sorted sequence is complete
+template <class L>
+constexpr int lanes_level(int band) {
+    int level = 0;
+    while ((1 << level) < L::parts(band)) ++level;
+    return level;
+}
+// does a band complete at this level?  (the levels without one are not dumped)
+template <class L>
+constexpr bool lanes_level_completes(int level) {
+    for (int b = 0; b < kLanesBands; ++b)
+        if (lanes_level<L>(b) == level) return true;
+    return false;
+}
+// a band of `count` rows over `parts` lanes: rows per part, the rows of part `part`, and whether the pair (last row of
+// this part, first row of the next) exists
+constexpr int lanes_rows_per_part(int count, int parts) { return (count + parts - 1) / parts; }
+constexpr int lanes_part_rows(int count, int h, int part) {
+    const int m = count - part * h;
+    return (m < 0) ? 0 : ((m > h) ? h : m);
+}
+constexpr bool lanes_bridge(int count, int h, int part, int parts) { return part + 1 < parts && count > (part + 1) * h; }
+// LDS slot of position `pos` of band `band` (hb: rows per part of every band; a column of `stride` doubles per lane):
+// lane-major, ascending.  A band of one part never leaves its lane: no rows-per-part is read for it.
+constexpr int kLanesOnePart = 1 << 20;
+template <class L>
+constexpr int lanes_slot(int band, int pos, const int (&hb)[kLanesBands], int stride) {
+    int lane = 0, h = kLanesOnePart;
+    for (int k = 0; k < kLanesBands; ++k)
+        if (band == k) {
+            lane = L::first_lane(k);
+            if (L::parts(k) > 1) h = hb[k];
+        }
+    int part = 0;
+    for (int q = 1; q < L::MAX_PARTS; ++q) part += (pos >= q * h) ? 1 : 0;
+    return (lane + part) * stride + (pos - part * h);
+}
 
 }  // namespace lcfe
 
@@ -203,32 +342,74 @@ __device__ __forceinline__ void lanes_order_stats(LanesBuf buf, int base, int m,
     mad = (r == m / 2) ? v_lo : (v_lo + v_hi) / 2.0;
 }
 
-// x of the partner lane of a split band (lanes 2|3 and 6|7 of a group)
-__device__ __forceinline__ double lanes_pair(double x) { return lane_xor_fetch<1>(x); }
-__device__ __forceinline__ int lanes_pair(int x) { return lane_xor_fetch<1>(x); }
+// op over the lanes of one band (`parts` of them, an aligned block): every lane of the band gets the result.  Per
+// layout: with one- and two-part bands the fetch sits under a branch, with two- and four-part bands both fetches are
+// made and one selected -- one form for both (fetch, then select per doubling) spilled 20 more VGPRs of
+// stat_lanes_all_kernel in the 8-lane routes.
+template <class L, class V, class Op>
+__device__ __forceinline__ V lanes_band(V x, int parts, Op op) {
+    if constexpr (L::MAX_PARTS == 2) {
+        if (parts == 2) x = op(x, lane_xor_fetch<1>(x));
+        return x;
+    } else {
+        static_assert(L::MAX_PARTS == 4, "one fetch per doubling");
+        const V x1 = op(x, lane_xor_fetch<1>(x));
+        const V x2 = op(x1, lane_xor_fetch<2>(x1));
+        return (parts == 4) ? x2 : x1;
+    }
+}
 
-// Eight light curves (one per 8-lane group: `obj` < 0 = none; CSR rows [s1, e1)) -> their 123 columns, or list
-// `fallback_list`.  ITERS = rows / 8 a light curve of the list may have (band code 256 = no row -- 255 is a code a file
+// Merge levels LEVEL .. log2(LPO) of the lanes' sorted registers.  A level at which a sequence completes is dumped to
+// LDS (lane-major); `reads`: this lane is the first of a band with rows and without NaN, and reads the band's extrema
+// and order statistics off the dump of the band's level.  The last dump (the light curve's rows) is left to the caller.
+template <class L, int CAP, int LEVEL>
+__device__ __forceinline__ void lanes_merge_levels(double (&w)[CAP], LanesBuf buf, int col, int j, bool reads, int parts, int mband,
+                                                   double& mn, double& mx, double& med, double& iqr, double& mad) {
+    using G = typename L::G;
+    constexpr bool last = (1 << LEVEL) == L::LPO;
+    if constexpr (LEVEL > 0) lane_merge<CAP, (1 << LEVEL) / 2>(w, j);
+    if constexpr (last || lanes_level_completes<L>(LEVEL)) {
+#pragma unroll
+        for (int i = 0; i < CAP; ++i) buf[col + i] = w[i];
+        G::sync();
+    }
+    if constexpr (!last) {
+        if constexpr (lanes_level_completes<L>(LEVEL)) {
+            if (reads && parts == (1 << LEVEL)) {
+                mn = buf[col];
+                mx = lanes_seq<CAP>(buf, col, mband - 1);
+                lanes_order_stats<CAP>(buf, col, mband, med, iqr, mad);
+            }
+            G::sync();
+        }
+        lanes_merge_levels<L, CAP, LEVEL + 1>(w, buf, col, j, reads, parts, mband, mn, mx, med, iqr, mad);
+    }
+}
+
+// 64 / LPO light curves (one per LPO-lane group: `obj` < 0 = none; CSR rows [s1, e1)) -> their 123 columns, or list
+// `fallback_list`.  ITERS = rows / LPO a light curve of the list may have (band code 256 = no row -- 255 is a code a file
 // may hold).  The rows are loaded in predicated blocks of four trips: one basic block of unconditional loads, a
 // persistent batch loop around this function, or exec-masked element loops all made the compiler spill hundreds of
 // registers (profiles/r02_stat_instruction_budget.md).
-template <int CAP, int ITERS>
+template <int LPO, int CAP, int ITERS>
 __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double* gf, const double* ge, const uint8_t* gb, int obj,
-                                              int64_t s1, int64_t e1, LanesBuf buf, LanesBuf all_rows, double* out, int ld, int col0,
-                                              int* fallback_list, int* fallback_count) {
-    using G = GroupDev<8>;
+                                                 int64_t s1, int64_t e1, LanesBuf buf, LanesBuf all_rows, double* out, int ld, int col0,
+                                                 int* fallback_list, int* fallback_count) {
+    using L = LanesLayout<LPO>;
+    using G = typename L::G;
     constexpr int STRIDE = StatLanesLds<CAP>::STRIDE;
     constexpr int BLK = 4;
     static_assert(ITERS % BLK == 0 && ITERS <= CAP, "rows per lane");
-    const int lane = threadIdx.x & 63, j = lane & 7, g8 = lane & 56;
+    const int lane = threadIdx.x & 63, j = lane & (LPO - 1), g0 = lane & ~(LPO - 1);
     const int n = (int)(e1 - s1);
     const bool has_obj = obj >= 0;
-    bool fit = has_obj && n >= 1 && n <= 8 * ITERS;
+    bool fit = has_obj && n >= 1 && n <= LPO * ITERS;
     const int nr = fit ? n : 0;
     int nmax = 0;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { const int v_ = __builtin_amdgcn_readlane(nr, 8 * k); nmax = (v_ > nmax) ? v_ : nmax; }
-    const int iters = (nmax + 7) >> 3;
+    for (int k = 0; k < 64 / LPO; ++k) { const int v_ = __builtin_amdgcn_readlane(nr, LPO * k); nmax = (v_ > nmax) ? v_ : nmax; }
+    constexpr int LOG = (LPO == 8) ? 3 : 4;                 // (shifts: the compiler does not know nmax >= 0)
+    const int iters = (nmax + LPO - 1) >> LOG;
     // ---- rows -> registers
     double rt[ITERS], rf[ITERS], rq[ITERS];
     int code[ITERS];
@@ -240,7 +421,7 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
             if (i0 < iters) {
 #pragma unroll
                 for (int q = 0; q < BLK; ++q) {
-                    const int row = (i0 + q) * 8 + j;
+                    const int row = (i0 + q) * LPO + j;
                     const bool ok = row < nr;
                     code[i0 + q] = ok ? (int)pb[row] : 256;
                     rt[i0 + q] = ok ? pt[row] : 0.0;
@@ -251,8 +432,8 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
         }
     }
 
-    // ---- A: slot of every row inside its band = rows of that band before it (ballots over the 8 rows of a trip)
-    int cnt[6] = {0, 0, 0, 0, 0, 0};
+    // ---- A: slot of every row inside its band = rows of that band before it (ballots over the LPO rows of a trip)
+    int cnt[kLanesBands] = {0, 0, 0, 0, 0, 0};
     bool known = true;
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
@@ -262,27 +443,61 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
             unsigned int mine = 0;
             int c0 = 0;
 #pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const unsigned int m8 = (unsigned int)(__ballot(b == k) >> g8) & 0xFFu;
-                if (b == k) { mine = m8; c0 = cnt[k]; }
-                cnt[k] += __builtin_popcount(m8);
+            for (int k = 0; k < kLanesBands; ++k) {
+                const unsigned int mk = (unsigned int)(__ballot(b == k) >> g0) & ((1u << LPO) - 1u);
+                if (b == k) { mine = mk; c0 = cnt[k]; }
+                cnt[k] += __builtin_popcount(mk);
             }
             const int pos = c0 + __builtin_popcount(mine & ((1u << j) - 1u));
             code[it] = ((b < 6) ? b : 7) | (pos << 8);
         }
     }
-    fit = fit && G::all(known) && cnt[0] <= CAP && cnt[1] <= CAP && cnt[4] <= CAP && cnt[5] <= CAP && cnt[2] <= 2 * CAP &&
-          cnt[3] <= 2 * CAP;
+    fit = fit && G::all(known);
+    // rows per part of every band
+    int hb[kLanesBands];
+#pragma unroll
+    for (int k = 0; k < kLanesBands; ++k) {
+        fit = fit && lanes_band_fits<L>(k, cnt[k], CAP);
+        hb[k] = lanes_rows_per_part(cnt[k], L::parts(k));
+    }
     const int N = fit ? n : 0;
-    const int h1r = (cnt[2] + 1) >> 1, h1i = (cnt[3] + 1) >> 1;
-    // this lane's share: band, rows
-    const int band = (j == 0) ? 0 : (j == 1) ? 1 : (j <= 3) ? 2 : (j == 4) ? 4 : (j == 5) ? 5 : 3;
-    const bool split = (j & 2) != 0, first = split && (j & 1) == 0;
-    int mband = (band == 0) ? cnt[0] : (band == 1) ? cnt[1] : (band == 2) ? cnt[2] : (band == 3) ? cnt[3] : (band == 4) ? cnt[4] : cnt[5];
-    const int h1 = (band == 2) ? h1r : h1i;
-    int m = !split ? mband : (first ? h1 : mband - h1);
-    if (!fit) { m = 0; mband = 0; }
-    const bool bridge = first && mband > m;                 // the pair (last row of the first half, first row of the second)
+    // this lane's share: band, part, rows = lanes_part_rows / lanes_bridge of the layout's tables (the debug build
+    // checks that).  Written out per layout: lookups over the tables (a chain over j == l, one over band == k) moved the
+    // register allocation of the 32-rows-per-lane routes -- with the slot expression below 12 -> 68 spilled VGPRs.
+    int band, part, parts, mband, h, m;
+    bool bridge;                                            // the pair (last row of this part, first row of the next)
+    if constexpr (LPO == 8) {
+        band = (j == 0) ? 0 : (j == 1) ? 1 : (j <= 3) ? 2 : (j == 4) ? 4 : (j == 5) ? 5 : 3;
+        const bool split = (j & 2) != 0, first_ = split && (j & 1) == 0;
+        mband = (band == 0) ? cnt[0] : (band == 1) ? cnt[1] : (band == 2) ? cnt[2] : (band == 3) ? cnt[3] : (band == 4) ? cnt[4] : cnt[5];
+        h = (band == 2) ? hb[2] : hb[3];
+        m = !split ? mband : (first_ ? h : mband - h);
+        if (!fit) { m = 0; mband = 0; }
+        bridge = first_ && mband > m;
+        part = (split && !first_) ? 1 : 0;
+        parts = split ? 2 : 1;
+    } else {
+        band = (j < 2) ? 0 : (j < 4) ? 1 : (j < 8) ? 2 : (j < 10) ? 4 : (j < 12) ? 5 : 3;
+        const bool four = (band == 2 || band == 3);
+        part = four ? (j & 3) : (j & 1);
+        parts = four ? 4 : 2;
+        mband = (band == 0) ? cnt[0] : (band == 1) ? cnt[1] : (band == 2) ? cnt[2] : (band == 3) ? cnt[3] : (band == 4) ? cnt[4] : cnt[5];
+        h = (band == 0) ? hb[0] : (band == 1) ? hb[1] : (band == 2) ? hb[2] : (band == 3) ? hb[3] : (band == 4) ? hb[4] : hb[5];
+        m = mband - part * h;
+        m = (m < 0) ? 0 : ((m > h) ? h : m);
+        int m_next = mband - (part + 1) * h;
+        m_next = (part + 1 < parts && m_next > 0) ? 1 : 0;
+        if (!fit) { m = 0; mband = 0; m_next = 0; }
+        bridge = m_next != 0;
+    }
+#ifdef LCFE_DEBUG
+    buf.bad[0] += (band != L::band_of(j & (LPO - 1)) || part != lanes_part_of<L>(j & (LPO - 1)) || parts != L::parts(band) ||
+                   (fit && (m != lanes_part_rows(mband, lanes_rows_per_part(mband, parts), part) ||
+                            bridge != lanes_bridge(mband, lanes_rows_per_part(mband, parts), part, parts))))
+                      ? 1u
+                      : 0u;
+#endif
+    const bool first = part == 0;
     const int col = lane * STRIDE;
 
     // ---- per row: LDS slot (-1: none); the all-rows slope and the order check from the file neighbours (row + 1 = next
@@ -294,16 +509,27 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
     for (int it = 0; it < ITERS; ++it) {
         if ((it & ~(BLK - 1)) < iters) {
             const int b = code[it] & 0xFF, pos = code[it] >> 8;
-            const bool second = (b == 2 && pos >= h1r) || (b == 3 && pos >= h1i);
-            const int hb = (b == 2) ? h1r : h1i;
-            const int dl = (b == 0) ? 0 : (b == 1) ? 1 : (b == 2) ? 2 : (b == 3) ? 6 : (b == 4) ? 4 : 5;
-            code[it] = (b < 6 && fit) ? (g8 + dl + (second ? 1 : 0)) * STRIDE + (second ? pos - hb : pos) : -1;
-            const int row = it * 8 + j;
+            // (= g0 * STRIDE + lanes_slot<L>(b, pos, hb, STRIDE); per layout for the same reason, checked by the debug build)
+            if constexpr (LPO == 8) {
+                const bool second = (b == 2 && pos >= hb[2]) || (b == 3 && pos >= hb[3]);
+                const int hs = (b == 2) ? hb[2] : hb[3];
+                const int dl = (b == 0) ? 0 : (b == 1) ? 1 : (b == 2) ? 2 : (b == 3) ? 6 : (b == 4) ? 4 : 5;
+                code[it] = (b < 6 && fit) ? (g0 + dl + (second ? 1 : 0)) * STRIDE + (second ? pos - hs : pos) : -1;
+            } else {
+                const int hh = (b == 0) ? hb[0] : (b == 1) ? hb[1] : (b == 2) ? hb[2] : (b == 3) ? hb[3] : (b == 4) ? hb[4] : hb[5];
+                const int jb = (b == 0) ? 0 : (b == 1) ? 2 : (b == 2) ? 4 : (b == 3) ? 12 : (b == 4) ? 8 : 10;
+                const int p = ((pos >= hh) ? 1 : 0) + ((pos >= 2 * hh) ? 1 : 0) + ((pos >= 3 * hh) ? 1 : 0);
+                code[it] = (b < 6 && fit) ? (g0 + jb + p) * STRIDE + (pos - p * hh) : -1;
+            }
+#ifdef LCFE_DEBUG
+            buf.bad[0] += (b < 6 && fit && code[it] != g0 * STRIDE + lanes_slot<L>(b, pos, hb, STRIDE)) ? 1u : 0u;
+#endif
+            const int row = it * LPO + j;
             const bool has = row + 1 < N;
-            const double tn_l = G::template dpp<0x101>(rt[it]), fn_l = G::template dpp<0x101>(rf[it]);   // row_shl:1
-            const double tn_w = G::template dpp<0x117>(rt[(it + 1 < ITERS) ? it + 1 : it]),              // row_shr:7
-                         fn_w = G::template dpp<0x117>(rf[(it + 1 < ITERS) ? it + 1 : it]);
-            const double t1 = (j == 7) ? tn_w : tn_l, f1 = (j == 7) ? fn_w : fn_l;
+            const double tn_l = WaveDev::dpp<0x101>(rt[it]), fn_l = WaveDev::dpp<0x101>(rf[it]);        // row_shl:1
+            const double tn_w = WaveDev::dpp<L::WRAP_DPP>(rt[(it + 1 < ITERS) ? it + 1 : it]),
+                         fn_w = WaveDev::dpp<L::WRAP_DPP>(rf[(it + 1 < ITERS) ? it + 1 : it]);
+            const double t1 = (j == LPO - 1) ? tn_w : tn_l, f1 = (j == LPO - 1) ? fn_w : fn_l;
             ordered = ordered && !(has && !(rt[it] <= t1));
             const double dt = t1 - rt[it];
             const double sl = stat_slope(f1 - rf[it], dt);
@@ -325,7 +551,8 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
     double v[CAP];
 #pragma unroll
     for (int i = 0; i < CAP; ++i) v[i] = buf[col + i];
-    const double f_last = buf[col + ((m > 0) ? m - 1 : 0)], f_next = buf[col + STRIDE - ((j == 7) ? STRIDE : 0)];
+    // (the next lane's first row: read only where `bridge` holds; the wavefront's last lane has no next column)
+    const double f_last = buf[col + ((m > 0) ? m - 1 : 0)], f_next = buf[col + ((lane < 63) ? STRIDE : 0)];
     double s;
     bool nanf = false;
     {
@@ -389,30 +616,48 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
     }
     G::sync();
 
-    // ---- pass-1 totals: per band (the two halves of r and i combined) and over the light curve
+    // ---- pass-1 totals: over the light curve, and per band (the lanes of the band combined; a part without rows has no
+    //      first or last time)
     const double sA = G::sum(s), snrA = G::sum(snr);
     const int nsnrA = G::sum(nsnr);
     const bool nanA = G::any(nanf);
     const double a_slopeA = G::max(a_slope);
     const bool a_snanA = G::any(a_snan);
     const bool orderedA = G::all(ordered);
-    const double tmnA = G::min((m > 0) ? tmn : __builtin_inf()), tmxA = G::max((m > 0) ? tmx : -__builtin_inf());
-    if (split) {
-        const int p_nan = lanes_pair(nanf ? 1 : 0), p_snan = lanes_pair(snan ? 1 : 0);   // fetched by every lane (no short-circuit)
-        s += lanes_pair(s);
-        snr += lanes_pair(snr);
-        nsnr += lanes_pair(nsnr);
-        nanf = nanf | (p_nan != 0);
-        const double p_tmn = lanes_pair(tmn), p_tmx = lanes_pair(tmx), p_slope = lanes_pair(slope);
-        const int p_m = mband - m;
-        tmn = first ? tmn : p_tmn;                     // a band with rows has rows in its first half
-        tmx = first ? ((p_m > 0) ? p_tmx : tmx) : ((m > 0) ? tmx : p_tmx);
-        slope = (p_slope > slope) ? p_slope : slope;
-        snan = snan | (p_snan != 0);
+    tmn = (m > 0) ? tmn : __builtin_inf();
+    tmx = (m > 0) ? tmx : -__builtin_inf();
+    const double tmnA = G::min(tmn), tmxA = G::max(tmx);
+    auto add = [](auto a, auto b) { return a + b; };
+    auto mxo = [](auto a, auto b) { return (b > a) ? b : a; };
+    auto mno = [](auto a, auto b) { return (b < a) ? b : a; };
+    // (LPO = 8: the fetches of a pass under ONE branch on the split lanes, not one per value -- 1 -> 0 spilled VGPRs in its
+    //  routes, which the whole kernel needs to stay at the 25 it had)
+    if constexpr (LPO == 8) {
+        if (parts == 2) {
+            const int p_nan = lane_xor_fetch<1>(nanf ? 1 : 0), p_snan = lane_xor_fetch<1>(snan ? 1 : 0);
+            s += lane_xor_fetch<1>(s);
+            snr += lane_xor_fetch<1>(snr);
+            nsnr += lane_xor_fetch<1>(nsnr);
+            nanf = nanf | (p_nan != 0);
+            const double p_tmn = lane_xor_fetch<1>(tmn), p_tmx = lane_xor_fetch<1>(tmx), p_slope = lane_xor_fetch<1>(slope);
+            tmn = (p_tmn < tmn) ? p_tmn : tmn;
+            tmx = (p_tmx > tmx) ? p_tmx : tmx;
+            slope = (p_slope > slope) ? p_slope : slope;
+            snan = snan | (p_snan != 0);
+        }
+    } else {
+        s = lanes_band<L>(s, parts, add);
+        snr = lanes_band<L>(snr, parts, add);
+        nsnr = lanes_band<L>(nsnr, parts, add);
+        nanf = lanes_band<L>(nanf ? 1 : 0, parts, mxo) != 0;
+        snan = lanes_band<L>(snan ? 1 : 0, parts, mxo) != 0;
+        slope = lanes_band<L>(slope, parts, mxo);
+        tmn = lanes_band<L>(tmn, parts, mno);
+        tmx = lanes_band<L>(tmx, parts, mxo);
     }
     const double mean = s / mband, meanA = sA / N;
-    LanesBuf oa = all_rows + (g8 >> 3) * 17;              // the all-rows columns leave the registers as soon as they are known
-    if (j == 3) {
+    LanesBuf oa = all_rows + (g0 >> LOG) * 17;             // the all-rows columns leave the registers as soon as they are known
+    if (j == L::ALL_ROWS_LANE) {
         oa[0] = (double)N;
         oa[1] = meanA;
         oa[13] = (N > 1) ? (a_snanA ? qnan() : (a_slopeA < 0 ? 0.0 : a_slopeA)) : 0.0;
@@ -439,7 +684,7 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
         m2A = aA[0] + aA[1];
     }
     m2A = G::sum(m2A);
-    if (split) m2 += lanes_pair(m2);
+    m2 = lanes_band<L>(m2, parts, add);
     const double sd = (mband > 1) ? sqrt(m2 / mband) : 0.0, sdA = (N > 1) ? sqrt(m2A / N) : 0.0;
 
     // ---- pass 3 (the lanes of a light curve whose spread is not positive carry garbage that is dropped below)
@@ -472,11 +717,18 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
     s4A = G::sum(s4A);
     c1A = G::sum(c1A);
     c2A = G::sum(c2A);
-    if (split) {
-        s3 += lanes_pair(s3);
-        s4 += lanes_pair(s4);
-        c1 += lanes_pair(c1);
-        c2 += lanes_pair(c2);
+    if constexpr (LPO == 8) {
+        if (parts == 2) {
+            s3 += lane_xor_fetch<1>(s3);
+            s4 += lane_xor_fetch<1>(s4);
+            c1 += lane_xor_fetch<1>(c1);
+            c2 += lane_xor_fetch<1>(c2);
+        }
+    } else {
+        s3 = lanes_band<L>(s3, parts, add);
+        s4 = lanes_band<L>(s4, parts, add);
+        c1 = lanes_band<L>(c1, parts, add);
+        c2 = lanes_band<L>(c2, parts, add);
     }
     auto finish = [](int cnt_, double sd_, double s3_, double s4_, int c1_, int c2_, double& skew, double& kurt, double& b1, double& b2) {
         skew = 0.0; kurt = 0.0; b1 = 0.0; b2 = 0.0;
@@ -493,7 +745,7 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
     double skew, kurt, b1, b2, skewA, kurtA, b1A, b2A;
     finish(mband, sd, s3, s4, c1, c2, skew, kurt, b1, b2);
     finish(N, sdA, s3A, s4A, c1A, c2A, skewA, kurtA, b1A, b2A);
-    if (j == 3) {
+    if (j == L::ALL_ROWS_LANE) {
         oa[2] = sdA;
         oa[6] = skewA;
         oa[7] = kurtA;
@@ -501,44 +753,22 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
         oa[12] = b2A;
     }
 
-
-    // ---- order statistics and extrema: register sort per lane, then merges across the lanes
+    // ---- order statistics and extrema: register sort per lane, then merges across the lanes; a sequence's extrema
+    //      and order statistics are read off the LDS dump of the level that completes it
     double w[CAP];
 #pragma unroll
     for (int i = 0; i < CAP; ++i) w[i] = (i < m) ? v[i] : __builtin_inf();
     reg_sort<CAP>(w);
-    double mn = w[0], mx = -__builtin_inf();                // the maximum is read off the dumps (rank rows - 1)
-    double med = qnan(), iqr = qnan(), mad = qnan();
-#pragma unroll
-    for (int i = 0; i < CAP; ++i) buf[col + i] = w[i];
-    G::sync();
-    if (m > 0) mx = buf[col + m - 1];
-    if (!split && m > 0 && !nanf) lanes_order_stats<CAP>(buf, col, m, med, iqr, mad);
-    G::sync();
-    double mnA = G::min(mn), mxA = G::max(mx);
-    if (split) {
-        mn = dmin(mn, lanes_pair(mn));
-        mx = dmax(mx, lanes_pair(mx));
-    }
-    lane_merge<CAP, 1>(w, j);
-#pragma unroll
-    for (int i = 0; i < CAP; ++i) buf[col + i] = w[i];
-    G::sync();
-    if (first && mband > 0 && !nanf) lanes_order_stats<CAP>(buf, col, mband, med, iqr, mad);
-    G::sync();
-    lane_merge<CAP, 2>(w, j);
-    lane_merge<CAP, 4>(w, j);
-#pragma unroll
-    for (int i = 0; i < CAP; ++i) buf[col + i] = w[i];
-    G::sync();
-    double medA = qnan(), iqrA = qnan(), madA = qnan();
-    if (j == 3 && N > 0 && !nanA) lanes_order_stats<CAP>(buf, g8 * STRIDE, N, medA, iqrA, madA);
-    G::sync();
-    if (mband <= 1) iqr = 0.0;                               // statistical.py:86: 0 unless the group has two rows
-    if (N <= 1) iqrA = 0.0;
-    if (nanf) { mn = qnan(); mx = qnan(); }
-    if (nanA) { mnA = qnan(); mxA = qnan(); }
-    if (j == 3) {
+    double mn = qnan(), mx = qnan(), med = qnan(), iqr = qnan(), mad = qnan();
+    lanes_merge_levels<L, CAP, 0>(w, buf, col, j, first && mband > 0 && !nanf, parts, mband, mn, mx, med, iqr, mad);
+    if (j == L::ALL_ROWS_LANE) {
+        double mnA = qnan(), mxA = qnan(), medA = qnan(), iqrA = qnan(), madA = qnan();
+        if (N > 0 && !nanA) {
+            mnA = buf[g0 * STRIDE];
+            mxA = lanes_seq<CAP>(buf, g0 * STRIDE, N - 1);
+            lanes_order_stats<CAP>(buf, g0 * STRIDE, N, medA, iqrA, madA);
+        }
+        if (N <= 1) iqrA = 0.0;
         oa[3] = mnA;
         oa[4] = mxA;
         oa[8] = mxA - mnA;
@@ -546,20 +776,20 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
         oa[9] = madA;
         oa[10] = iqrA;
     }
+    G::sync();
+    if (mband <= 1) iqr = 0.0;                               // statistical.py:86: 0 unless the group has two rows
 
     // ---- the 123 columns of every light curve -> LDS rows -> global
-    LanesBuf o = buf + (g8 >> 3) * 128;
-    if (fit) {
-        if (!split || first) {
-            double* ob = lanes_raw(o + 17 * band, 17);
-            if (mband == 0) stat_empty_group(ob, nullptr);
-            else stat_write17(ob, mband, mean, sd, mn, mx, med, skew, kurt, mad, iqr, b1, b2, slope, snan, snr, nsnr, tmn, tmx);
-        }
+    LanesBuf o = buf + (g0 >> LOG) * 128;
+    if (fit && first) {
+        double* ob = lanes_raw(o + 17 * band, 17);
+        if (mband == 0) stat_empty_group(ob, nullptr);
+        else stat_write17(ob, mband, mean, sd, mn, mx, med, skew, kurt, mad, iqr, b1, b2, slope, snan, snr, nsnr, tmn, tmx);
     }
     G::sync();
     if (fit) {
 #pragma unroll
-        for (int c = j; c < 17; c += 8) o[102 + c] = oa[c];
+        for (int c = j; c < 17; c += LPO) o[102 + c] = oa[c];
     }
     G::sync();
     if (fit && j == 0) stat_cross_band(lanes_raw(o, STAT_NCOL));
@@ -567,8 +797,8 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
     // rows to global memory, one light curve at a time on the whole wavefront (two 512-byte stores per row)
     const bool done = fit && orderedA;
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int obj_r = __builtin_amdgcn_readlane(done ? obj : -1, 8 * r);
+    for (int r = 0; r < 64 / LPO; ++r) {
+        const int obj_r = __builtin_amdgcn_readlane(done ? obj : -1, LPO * r);
         if (obj_r >= 0) {
             double* row = out + (int64_t)obj_r * ld + col0;
             LanesBuf src = buf + r * 128;
@@ -583,13 +813,13 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
     G::sync();
 }
 
-// One workgroup = one batch (`batch`) of eight consecutive list entries; `buf`: 64 x (CAP + 1) doubles of LDS.
-template <int CAP, int ITERS>
+// One workgroup = one batch (`batch`) of 64 / LPO consecutive list entries; `buf`: 64 x (CAP + 1) doubles of LDS.
+template <int LPO, int CAP, int ITERS>
 __device__ __forceinline__ void stat_lanes_run(const int64_t* offsets, const double* gt, const double* gf, const double* ge,
                                                const uint8_t* gb, const int* list, int count, int batch, LanesBuf buf, LanesBuf all_rows,
                                                double* out, int ld, int col0, int* fallback_list, int* fallback_count) {
-    const int g = (threadIdx.x & 63) >> 3;
-    const int64_t base = (int64_t)batch * 8;
+    const int g = (threadIdx.x & 63) / LPO;
+    const int64_t base = (int64_t)batch * (64 / LPO);
     int obj = -1;
     int64_t s1 = 0, e1 = 0;
     if (base + g < count) {
@@ -597,7 +827,7 @@ __device__ __forceinline__ void stat_lanes_run(const int64_t* offsets, const dou
         s1 = offsets[obj];
         e1 = offsets[obj + 1];
     }
-    stat_lanes_batch<CAP, ITERS>(gt, gf, ge, gb, obj, s1, e1, buf, all_rows, out, ld, col0, fallback_list, fallback_count);
+    stat_lanes_batch<LPO, CAP, ITERS>(gt, gf, ge, gb, obj, s1, e1, buf, all_rows, out, ld, col0, fallback_list, fallback_count);
 }
 
 }  // namespace lcfe

@@ -138,7 +138,7 @@ def lane_route_objects():
 
 
 def test_statistics_lane_routes():
-    """The eight- and four-light-curves-per-wavefront statistics kernels (stat_lanes.hpp, stat_lanes16.hpp): band lengths
+    """The eight- and four-light-curves-per-wavefront statistics kernels (stat_lanes.hpp, LanesLayout<8> and <16>): band lengths
     on both sides of every routing threshold of the plan kernels (16- / 32-row lanes, 8 / 16 lanes per light curve, r and i
     over two / four lanes, 128 / 256 / 512 rows), bands of
     0 / 1 / 2 rows, odd and even r / i halves, negative and zero times, NaN and inf fluxes in either half, rows out of
@@ -185,7 +185,7 @@ def _lane_route_fill(objs, rng):
               [3, 9, 31, 30, 20, 7], [10, 20, 41, 40, 30, 12], [4, 4, 64, 4, 4, 4], [4, 4, 4, 64, 4, 48],
               [8, 8, 40, 40, 16, 16], [20, 20, 20, 20, 24, 24], [30, 30, 60, 60, 30, 30], [12, 12, 48, 47, 5, 5]):
         add(c)
-    # 16 lanes per light curve (stat_lanes16.hpp): bands of up to 64 rows (r, i: 128) in up to 512 rows, on both sides
+    # 16 lanes per light curve (stat_lanes.hpp, LanesLayout<16>): bands of up to 64 rows (r, i: 128) in up to 512 rows, on both sides
     # of the thresholds, four-part splits with uneven parts, parts that stay empty
     for c in ([64, 64, 128, 128, 64, 64], [65, 64, 128, 128, 64, 63], [64, 64, 129, 127, 64, 64], [33, 10, 70, 75, 40, 12],
               [10, 10, 101, 99, 10, 10], [1, 0, 97, 3, 33, 2], [40, 0, 0, 0, 0, 41], [0, 0, 5, 0, 0, 33], [60, 60, 60, 60, 8, 8],
