@@ -218,6 +218,35 @@ int lcfe_augment_device(int device, void* stream, int64_t n_obj, int64_t n_point
                         double* d_flux_out, double* d_err_out, uint8_t* d_band_out, int64_t* d_n_points_out,
                         void* d_workspace, size_t workspace_bytes);
 
+/*
+ * Sequence tensors on the device (models/lightcurve_dataset.py:79-127, 141-170, LightcurveDataset): a device-resident CSR
+ * batch -- a staged one or the output of lcfe_augment_device -- to the padded float32 inputs of the sequence classifiers.
+ * No feature set: no mask bit, no columns.  Like lcfe_extract_device: every pointer is a DEVICE pointer on `device`, the
+ * kernel is enqueued on `stream`, the call does not synchronise and allocates nothing.
+ * Per object of n rows, with L = max_length:
+ *   order     by (time, file index) over all bands, NaN times last; the first min(n, L) rows are kept
+ *   time      float32(t) - min over all n rows of float32(t), in float32
+ *   flux      float32(flux), NaN / +-inf -> 0; err: float32(err), NaN / +-inf -> 1, then max(err, 0.01f)
+ *   z-score   mean and population std of the cleaned float32 flux over ALL n rows, accumulated in fp64 and rounded to
+ *             float32 once; if `normalize` is non-zero and std > 1e-6f: flux = (flux - mean) / (std + 1e-6f),
+ *             err = err / (std + 1e-6f), in float32
+ *   delta_t   0 for the first row, (time[i] - time[i - 1]) / 30.0f after it
+ *   padding   time 0, flux 0, err 1, delta_t 0, band 0, mask 0
+ *   n == 0    length 1, row 0 = (0, 0, 1, 0), band 1, mask 1
+ * Outputs: features float32[n_obj, L, 4] = (time, flux, err, delta_t), aligned to 16 bytes; bands int64[n_obj, L], the band
+ * code of the batch (0..5 = u, g, r, i, z, y; 255 for an unknown filter); mask float32[n_obj, L]; length int64[n_obj];
+ * mean, std float32[n_obj]: what the z-score subtracted and divided by (std + 1e-6f), or 0 and 1 where none was applied.
+ * A light curve may have any number of rows (no buffer holds an object); one whose file order is not its time order costs
+ * n * n / 64 steps.  workspace: at least lcfe_sequences_workspace_bytes(n_obj, n_points, max_len) bytes, max_len the rows
+ * of the longest object; this version needs none (0 bytes: `workspace` may be NULL).  Errors (lcfe_last_error):
+ * max_length < 1, negative sizes, a NULL or misaligned required array, a workspace that is too small.
+ */
+size_t lcfe_sequences_workspace_bytes(int64_t n_obj, int64_t n_points, int64_t max_len);
+int lcfe_sequences_device(int device, void* stream, int64_t n_obj, int64_t n_points, int64_t max_length, int normalize,
+                          const int64_t* d_offsets, const double* d_t, const double* d_flux, const double* d_err,
+                          const uint8_t* d_band, float* d_features, int64_t* d_bands, float* d_mask, int64_t* d_length,
+                          float* d_mean, float* d_std, void* d_workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,11 @@ def load():
     lib.lcfe_augment_device.restype = ctypes.c_int
     lib.lcfe_augment_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + \
                                        [ctypes.c_void_p] * 21 + [ctypes.c_size_t]
+    lib.lcfe_sequences_workspace_bytes.restype = ctypes.c_size_t
+    lib.lcfe_sequences_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
+    lib.lcfe_sequences_device.restype = ctypes.c_int
+    lib.lcfe_sequences_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + \
+                                         [ctypes.c_void_p] * 12 + [ctypes.c_size_t]
     _lib = lib
     return lib
 

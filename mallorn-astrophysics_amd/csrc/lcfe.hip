@@ -22,6 +22,7 @@
 #include "stat_lanes.hpp"
 #include "gp1d.hpp"
 #include "augment.hpp"
+#include "sequence.hpp"
 
 using namespace lcfe;
 
@@ -1988,6 +1989,16 @@ __global__ __launch_bounds__(64 * kAugWaves) void augment_write_kernel(AugIn A, 
         aug_write_object<AugWave>(A, P, O, i, tmin, hist[threadIdx.x >> 6]);
 }
 
+// ---- sequence tensors (sequence.hpp): one wavefront per object, kSeqWaves objects per workgroup; the grid strides over
+// the objects.  No LDS and no workspace: an object is streamed from the batch.
+constexpr int kSeqWaves = 4;
+
+__global__ __launch_bounds__(64 * kSeqWaves) void sequences_kernel(SeqIn A, SeqOut O, int64_t n_obj, int64_t max_length, int normalize) {
+    const int64_t stride = (int64_t)gridDim.x * kSeqWaves;
+    for (int64_t i = (int64_t)blockIdx.x * kSeqWaves + (threadIdx.x >> 6); i < n_obj; i += stride)
+        seq_object<WaveOfBlock>(A, O, i, max_length, normalize != 0);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2424,6 +2435,41 @@ int lcfe_augment_device(int device, void* stream_, int64_t n_obj, int64_t n_poin
     hipLaunchKernelGGL(augment_scan_apply_kernel, dim3((unsigned)W.tiles), dim3(kAugScanThreads), 0, stream, d_offsets_out + 1, m, W.tile_sum);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(augment_write_kernel, dim3(grid), dim3(64 * kAugWaves), 0, stream, A, P, O, n_obj, W.tmin, W.flag);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+size_t lcfe_sequences_workspace_bytes(int64_t n_obj, int64_t n_points, int64_t max_len) {
+    (void)n_obj; (void)n_points; (void)max_len;
+    return 0;                               // every pass streams from the batch
+}
+
+int lcfe_sequences_device(int device, void* stream_, int64_t n_obj, int64_t n_points, int64_t max_length, int normalize,
+                          const int64_t* d_offsets, const double* d_t, const double* d_flux, const double* d_err, const uint8_t* d_band,
+                          float* d_features, int64_t* d_bands, float* d_mask, int64_t* d_length, float* d_mean, float* d_std,
+                          void* d_workspace, size_t workspace_bytes) {
+    g_err.clear();
+    if (max_length < 1) return fail_msg("lcfe_sequences_device: max_length must be at least 1");
+    if (n_obj < 0 || n_points < 0) return fail_msg("lcfe_sequences_device: negative size");
+    if (n_obj > (INT64_MAX >> 5) / max_length) return fail_msg("lcfe_sequences_device: n_obj * max_length overflows");
+    if (!d_offsets) return fail_msg("lcfe_sequences_device: null offsets");
+    if (n_points > 0 && (!d_t || !d_flux || !d_err || !d_band)) return fail_msg("lcfe_sequences_device: null sample array");
+    if (n_obj > 0 && (!d_features || !d_bands || !d_mask || !d_length || !d_mean || !d_std))
+        return fail_msg("lcfe_sequences_device: null output array");
+    if ((uintptr_t)d_features & 15) return fail_msg("lcfe_sequences_device: features must be aligned to 16 bytes");
+    const size_t need = lcfe_sequences_workspace_bytes(n_obj, n_points, 0);
+    if (need > 0 && (!d_workspace || workspace_bytes < need))
+        return fail_msg("lcfe_sequences_device: workspace smaller than lcfe_sequences_workspace_bytes(n_obj, n_points, max_len)");
+    if (n_obj == 0) return 0;
+    DeviceGuard guard;
+    if (guard.enter(device)) return fail_msg("lcfe_sequences_device: cannot select device " + std::to_string(device));
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const SeqIn A{d_offsets, d_t, d_flux, d_err, d_band};
+    const SeqOut O{reinterpret_cast<SeqRow*>(d_features), d_bands, d_mask, d_length, d_mean, d_std};
+    const int64_t groups = (n_obj + kSeqWaves - 1) / kSeqWaves, cap = (int64_t)num_cus(dev) * 8;
+    const unsigned grid = (unsigned)((groups < cap) ? groups : cap);
+    hipLaunchKernelGGL(sequences_kernel, dim3(grid), dim3(64 * kSeqWaves), 0, (hipStream_t)stream_, A, O, n_obj, max_length, normalize);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -199,3 +199,29 @@ class DeviceBatch:
         new.z = None if self.z is None else self.z.repeat_interleave(k)
         new.max_len = int(torch.diff(new.offsets).max().item()) if new.n_obj else 0
         return new
+
+    def sequences(self, max_length=500, normalize_flux=True):
+        """The padded float32 inputs of the sequence classifiers (the reference's ``LightcurveDataset``), one row per object,
+        as torch tensors on the batch's device (``lcfe_sequences_device`` on the current stream): ``features``
+        [n_obj, max_length, 4] = (time, flux, flux_err, delta_t), ``bands`` int64 and ``mask`` float32 [n_obj, max_length],
+        ``length`` int64 [n_obj], and ``flux_mean`` / ``flux_std`` float32 [n_obj] -- what the z-score subtracted and divided
+        by (0 and 1 where it was not applied), so ``flux * flux_std + flux_mean`` undoes it.  An object without rows is the
+        reference's empty sequence.  The batch is left as it is: a staged batch and the one ``augment`` returns work alike."""
+        torch = self.torch
+        lib = _lib.load()
+        L = int(max_length)
+        if L < 1:
+            raise ValueError("max_length must be at least 1")
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        out = {"features": new((self.n_obj, L, 4), torch.float32), "bands": new((self.n_obj, L), torch.int64),
+               "mask": new((self.n_obj, L), torch.float32), "length": new((self.n_obj,), torch.int64),
+               "flux_mean": new((self.n_obj,), torch.float32), "flux_std": new((self.n_obj,), torch.float32)}
+        wsb = int(lib.lcfe_sequences_workspace_bytes(self.n_obj, self.n_points, self.max_len))
+        ws = new((wsb,), torch.uint8) if wsb else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
+        rc = lib.lcfe_sequences_device(self.device.index, ctypes.c_void_p(stream), self.n_obj, self.n_points, L, int(bool(normalize_flux)),
+                                       p(self.offsets), p(self.t), p(self.flux), p(self.err), p(self.band), *[p(a) for a in out.values()],
+                                       p(ws), wsb)
+        _lib.check(rc, "lcfe_sequences_device")
+        return out
