@@ -166,6 +166,23 @@ __device__ __forceinline__ void gp_inv16_pivots(double (&p)[4], int a, int c, bo
 }
 #endif
 
+#if defined(__HIPCC__)
+// A pointer every lane holds (an argument of the not-inlined evaluation arrives in VGPRs), made wave-uniform so that it
+// lives in SGPRs and tile addresses become one scalar base plus a 32-bit lane offset (uniform by construction
+// is made uniform explicitly).
+template <class P>
+__device__ __forceinline__ P gp_uniform_ptr(P p) {
+    if constexpr (sizeof(P) == 4) {
+        return __builtin_bit_cast(P, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p)));
+    } else {
+        const unsigned long long u = __builtin_bit_cast(unsigned long long, p);
+        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
+        return __builtin_bit_cast(P, ((unsigned long long)hi << 32) | lo);
+    }
+}
+#endif
+
 // rank of tile row i in the snake that deals the rows (longest first) to the NW wavefronts
 LCFE_FN int gp_row_owner(int i, int nt, int nw) {
     const int k = nt - 1 - i, blk = k / nw, pos = k - blk * nw;
@@ -197,8 +214,14 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
     if constexpr (W::WAVE == 64) {
         constexpr int NW = W::NWAVES;
         constexpr int LDV = gp_panel_ld(NP);
-        const int l = W::wlane(), lr = l >> 4, lc = l & 15, w = W::wave_id();
-        double ld = 0.0, prod = 1.0;          // wavefront 0: exponent sum and mantissa product of the pivots
+        const int l = W::wlane(), lr = l >> 4, lc = l & 15, w = uniform_int(W::wave_id());
+        // wavefront 0: exponent sum and mantissa product of the pivots.  Between two inverses they wait in LDS (S.slot is
+        // free during an evaluation), not in four registers that are live across every update phase; the long-object tier
+        // (working set in global scratch, no look-ahead) keeps them in registers.
+        constexpr bool kParkAcc = LDS::kInLds;
+        double ld = 0.0, prod = 1.0;
+        auto acc_fetch = [&]() { if constexpr (kParkAcc) { prod = S.slot[0]; ld = S.slot[1]; } };
+        auto acc_park = [&]() { if constexpr (kParkAcc) { S.slot[0] = prod; S.slot[1] = ld; } };
 
         // (1) pivot tile column kt -> Vp[p][i] = A(i, 16 kt + p); rows p >= bs of the panel are zero.  Tiles below the
         //     pivot are copied (transposed) by the owner of their row, the tiles of the pivot row itself by all
@@ -263,7 +286,9 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
                 p[r] = (a < bs && b < bs) ? Vp[b][k0 + a] : ((a == b) ? 1.0 : 0.0);
             }
             bool bad = false;
+            acc_fetch();
             gp_inv16_pivots<0>(p, a, c, bad, prod, ld);
+            acc_park();
 #pragma unroll
             for (int r = 0; r < 4; ++r) Pp[a][4 * c + r] = -p[r];         // the sweep leaves -D^-1
             if (bad && l == 0) S.pivot_bad = 1;
@@ -293,7 +318,10 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
         // for the next step.  Tile rows are handed out by a ticket (longest first), so wavefront 0 simply takes fewer rows.
         // Operation for operation the arithmetic of the step-by-step schedule: bit-identical results.
         constexpr bool kLookAhead = LDS::kLookAhead;
-        double pn1[4] = {0, 0, 0, 0}, pn2[4] = {0, 0, 0, 0};      // wavefront 0: -(-D^-1) of the next pivot block(s), Gauss-Jordan layout
+        double pn1[4] = {0, 0, 0, 0};         // wavefront 0: -(-D^-1) of the next pivot block, Gauss-Jordan layout
+        // (the second inverse of a fused pass waits in the staging tile, which is idle from the end of one look-ahead to the
+        //  start of the next: the lane that wrote an element is the one that reads it back)
+        double (*Stage)[GP_B] = reinterpret_cast<double (*)[GP_B]>(S.la.stage);
         bool have1 = false, have2 = false;                         // (uniform) the next step's inverse(s) are already known
         auto grab_row = [&]() -> int {
             int r = 0;
@@ -321,7 +349,9 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
                 p[r] = (a < bs && bq < bs) ? x : ((a == bq) ? 1.0 : 0.0);
             }
             bool bad = false;
+            acc_fetch();
             gp_inv16_pivots<0>(p, a, cq, bad, prod, ld);
+            acc_park();
 #pragma unroll
             for (int r = 0; r < 4; ++r) pout[r] = -p[r];
             if (bad && l == 0) S.pivot_bad = 1;
@@ -330,6 +360,19 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
             const int a = l >> 2, cq = l & 3;
 #pragma unroll
             for (int r = 0; r < 4; ++r) Pp[a][4 * cq + r] = pin[r];
+        };
+        // One-tile-per-pass tiers whose alpha vector holds a tile (NP >= 256: the 768-row tier): the look-ahead inverse waits
+        // there for the next step.  alpha is written only after the sweep (gp_eval) and nobody reads it during one; S.P and
+        // fz.P2 are read by every wavefront during the current step and cannot take it.
+        constexpr bool kParkInv = kLookAhead && !LDS::kFuse && LDS::kInLds && NP * sizeof(double) >= GP_B * GP_B * sizeof(double);
+        double (*Park)[GP_B] = reinterpret_cast<double (*)[GP_B]>(S.alpha);
+        auto park_inv = [&](const double (&pin)[4]) { if constexpr (kParkInv) write_P(Park, pin); };
+        auto fetch_inv = [&](double (&pio)[4]) {
+            if constexpr (kParkInv) {
+                const int a = l >> 2, cq = l & 3;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pio[r] = Park[a][4 * cq + r];
+            }
         };
         // C_ij -= W_i V_j' with W_i in A layout (negated) against panel Vp
         auto rank16 = [&](gp_v4f64 c, const gp_v4f64& wt, double (*Vp)[LDV], int j) {
@@ -349,6 +392,7 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
         };
 
         if (W::lane() == 0) S.pivot_bad = 0;
+        if (w == 0) acc_park();               // (1, 0); the first inverse comes after a barrier
         int kt = 0, k0 = 0;
         while (k0 < n) {
             if constexpr (LDS::kFuse) {
@@ -363,7 +407,13 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
                     GP_T0();
                     gather(S.V, a, GP_B);
                     if (w == 0 && have1) write_P(S.P, pn1);
-                    if (w == 0 && have2) write_P(P2, pn2);
+                    if (w == 0 && have2) {
+                        const int ga = l >> 2, gc = l & 3;
+                        double pn2[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) pn2[r] = Stage[ga][4 * gc + r];
+                        write_P(P2, pn2);
+                    }
                     if (W::lane() == 0) S.row_ticket = 0;
                     W::sync();
                     GP_T(0);
@@ -442,7 +492,7 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
                         if (la2) {
                             // -D1'^-1 in A-operand layout (through the staging tile)
                             W::wave_sync();
-                            write_P(reinterpret_cast<double (*)[GP_B]>(S.la.stage), pn1);
+                            write_P(Stage, pn1);
                             W::wave_sync();
                             double dAn[4];
 #pragma unroll
@@ -467,7 +517,10 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
                             store_tile(Tbb, cbb);                        // steps a and b: what the next pass's step a2 starts from
 #pragma unroll
                             for (int kc = 0; kc < 4; ++kc) cbb = __builtin_amdgcn_mfma_f64_16x16x4f64(-wtn[kc], vb[kc], cbb, 0, 0, 0);
+                            double pn2[4];
                             stage_invert(cbb, GP_B, pn2);
+                            W::wave_sync();
+                            write_P(Stage, pn2);
                         }
                     }
                     // ---- both updates on every other tile, row by row
@@ -565,7 +618,7 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
             const int bs = (n - k0 < GP_B) ? n - k0 : GP_B;
             GP_T0();
             gather(S.V, kt, bs);
-            if (w == 0 && have1) write_P(S.P, pn1);
+            if (w == 0 && have1) { fetch_inv(pn1); write_P(S.P, pn1); }
             if (W::lane() == 0) S.row_ticket = 0;
             W::sync();
             GP_T(0);
@@ -586,6 +639,7 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
                 const gp_v4f64 c = rank16(load_tile(Tn), wn, S.V, kt + 1);
                 store_tile(Tn, c);
                 stage_invert(c, (rest < GP_B) ? rest : GP_B, pn1);
+                park_inv(pn1);
             }
             for (;;) {
                 const int i = grab_row();
@@ -664,6 +718,7 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
             k0 += GP_B;
         }
         // log|K| = (sum of exponents) ln 2 + log(mantissa product), known to wavefront 0
+        if (w == 0) acc_fetch();
         double tot = (w == 0) ? (ld * 0.6931471805599453 + log(prod)) : 0.0;
         logdet = W::bcast_from_first_wave(tot);
         return true;
@@ -747,19 +802,28 @@ LCFE_FN double gp_kernel_q(double q0, double q1, double c, double& e) {
 // grad_log_likelihood as wrapped by multiband_gp.py:141-154).  K is overwritten (by -K^-1).  On a
 // failed factorisation f = 1e25 and g = 0.  `need_grad` false: only alpha and f (prediction pass).
 template <class W, int NP, class KP, class LDS>
-LCFE_FN_NOINLINE void gp_eval(const double* p, int n, LDS& S, KP K, double& f, double* g, bool need_grad) {
+LCFE_FN_NOINLINE void gp_eval(const double* p, int n, LDS& S_arg, KP K, double& f, double* g, bool need_grad) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    // the evaluation is a function of its own, so its arguments arrive in VGPRs: the row count and the pointers to the
+    // working set and the matrix are the same in every lane and go to SGPRs before they steer loops and addresses
+    n = uniform_int(n);
+    K = gp_uniform_ptr(K);
+    LDS& S = *gp_uniform_ptr(&S_arg);
     if constexpr (LDS::kInLds) __builtin_assume(__builtin_amdgcn_is_shared((const void*)&S));    // ds_* addressing of the working set
+#else
+    LDS& S = S_arg;
 #endif
     const int lane = W::lane();
     constexpr int G = (W::LANES >= 64) ? 64 : W::LANES;
     constexpr int RG = W::LANES / G;
     const int rl = lane / G, cl = lane % G;
+    GP_T0();
+    // Gram matrix, tile-packed lower triangle.  (mean and kernel parameters live in this scope only: the gradient pass
+    // works them out again from p, the same operations on the same inputs, so that they are not carried across the sweep)
+    {
     const double mu = p[0], c = exp(p[1]), m0 = exp(p[2]), m1 = exp(p[3]);
     const double im0 = 1.0 / m0, im1 = 1.0 / m1;
     (void)im0; (void)im1;
-    GP_T0();
-    // Gram matrix, tile-packed lower triangle
 #if defined(__HIPCC__)
     if constexpr (W::WAVE == 64) {
         // every wavefront fills the tiles of the rows it owns in the sweep (D-operand layout: lane l, register v
@@ -809,6 +873,7 @@ LCFE_FN_NOINLINE void gp_eval(const double* p, int n, LDS& S, KP K, double& f, d
     }
     for (int i = lane; i <= n; i += W::LANES) K[tri_index(n, i)] = (i < n) ? S.y[i] - mu : 0.0;   // augmented row
     }
+    }
     W::sync();
     GP_T(4);
     double logdet;
@@ -831,6 +896,9 @@ LCFE_FN_NOINLINE void gp_eval(const double* p, int n, LDS& S, KP K, double& f, d
     if (!need_grad) return;
     // gradient: 0.5 * sum_ij (alpha_i alpha_j - Kinv_ij) dK_ij/dtheta ,  Kinv_ij = -K[ij]
     double g1 = 0, g2 = 0, g3 = 0;
+    const double c = exp(p[1]), m0 = exp(p[2]), m1 = exp(p[3]);
+    const double im0 = 1.0 / m0, im1 = 1.0 / m1;
+    (void)im0; (void)im1;
 #if defined(__HIPCC__)
     if constexpr (W::WAVE == 64) {
         constexpr int NW = W::NWAVES;
