@@ -157,6 +157,7 @@ LCFE_FN void wave_select_ranks(const double* x, int m, unsigned long long* keys,
 // i ^ J for J = K/4 ... 1; the lower index always keeps the minimum.  Partners closer than KPL are
 // other registers of the same lane, the rest are fetched from lane ^ (J / KPL) (DPP / swizzle).
 // The values must not contain NaN (callers branch on that before; pad with +inf).
+LCFE_FN bool sort_takes_partner(double own, double partner, bool keep_min) { return keep_min ? (partner < own) : (own < partner); }
 template <class W, int KPL, int K>
 LCFE_FN void sort_flip_step(double (&v)[KPL]) {
     if constexpr (K <= KPL) {
@@ -171,10 +172,11 @@ LCFE_FN void sort_flip_step(double (&v)[KPL]) {
         double p[KPL];
 #pragma unroll
         for (int r = 0; r < KPL; ++r) p[r] = W::template xfetch<ML>(v[KPL - 1 - r]);
-        // one compare + select instead of min, max and a select: the partner replaces the own value where
-        // "partner < own" agrees with "this lane keeps the minimum" (NaN-free data; equal values may swap freely)
+        // compare + select instead of min, max and a select: the partner replaces the own value where it is strictly
+        // smaller (this lane keeps the minimum) or strictly larger (it keeps the maximum).  Both lanes of a pair keep
+        // their own value when the two compare equal, so no bit pattern is duplicated or lost (+0 and -0).  NaN-free data.
 #pragma unroll
-        for (int r = 0; r < KPL; ++r) v[r] = ((p[r] < v[r]) == keep_min) ? p[r] : v[r];
+        for (int r = 0; r < KPL; ++r) v[r] = sort_takes_partner(v[r], p[r], keep_min) ? p[r] : v[r];
     }
 }
 template <class W, int KPL, int J>
@@ -191,7 +193,7 @@ LCFE_FN void sort_half_steps(double (&v)[KPL]) {
 #pragma unroll
             for (int r = 0; r < KPL; ++r) p[r] = W::template xfetch<ML>(v[r]);
 #pragma unroll
-            for (int r = 0; r < KPL; ++r) v[r] = ((p[r] < v[r]) == keep_min) ? p[r] : v[r];
+            for (int r = 0; r < KPL; ++r) v[r] = sort_takes_partner(v[r], p[r], keep_min) ? p[r] : v[r];
         }
         sort_half_steps<W, KPL, J / 2>(v);
     }

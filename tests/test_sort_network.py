@@ -1,7 +1,8 @@
 """The wiring of the register sorting network of csrc/stage.hpp (sort_flip_step / sort_half_steps /
 sort_merges), re-stated lane by lane in numpy: the same partner masks, register pairings and
 keep-min rules must sort every input for every (lanes, values-per-lane) shape the kernels
-instantiate.  (The device code itself is exercised by the GPU parity tests; this pins the design.)"""
+instantiate.  (The device code itself is run on its own by tests/test_gpu_lane_blocks.py::test_group_sort_values, and
+as part of the kernels by the GPU parity tests; this pins the design.)"""
 import numpy as np
 import pytest
 
