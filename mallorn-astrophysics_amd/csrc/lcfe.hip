@@ -21,6 +21,7 @@
 #include "stat_lean.hpp"
 #include "stat_lanes.hpp"
 #include "gp1d.hpp"
+#include "gp_tiers.hpp"
 #include "augment.hpp"
 #include "sequence.hpp"
 
@@ -161,9 +162,6 @@ struct SetLaunch {
 __device__ __forceinline__ int set_bin_of(int64_t n) {
     return (n <= 128) ? 0 : (n <= 256) ? 1 : (n <= 512) ? 2 : (n <= 1024) ? 3 : (n <= 2048) ? 4 : 6;
 }
-constexpr int kGpSmallNP = 240;     // matrix in global scratch, two pivot tiles per pass, two 512-thread workgroups per CU
-constexpr int kGpMidNP = 512;       // matrix in global scratch, two pivot tiles per pass, one 512-thread workgroup per CU
-constexpr int kGpGlobalNP = 768;    // matrix in global scratch, one pivot tile per pass (512..767 rows)
 // GP window on the ROW count of the object (>= its valid points); one row of the tile storage is the
 // augmented residual row, so the caps are NP - 1.
 __device__ __forceinline__ int gp_bin_of(int64_t n) {
@@ -1026,31 +1024,12 @@ constexpr int kGpSmallGrid = 512;
 constexpr size_t kGpSmallBytes = (size_t)kGpSmallGrid * gp_store_doubles(kGpSmallNP) * 8;
 constexpr size_t kGpMidBytes = (size_t)kGpGlobalGrid * gp_store_doubles(kGpMidNP) * 8;
 constexpr size_t kGpGlobalBytes = (size_t)kGpGlobalGrid * gp_store_doubles(kGpGlobalNP) * 8;
-// the 112- and 160-row tiers can keep their matrix in global scratch as well (L2-resident slabs): the LDS then holds
-// only the two pivot panels, two to four workgroups share a CU and the sweep takes two pivot tiles per pass.  Measured
-// (125,000 objects): serialised, both tiers gain 8-9 %; with the fit kernels running beside the GP (the default
-// schedule) the 112-row tier in global scratch gains 1.5 % end to end and the 160-row tier LOSES 5 % -- so only the former.
-constexpr bool kGp112Global = true, kGp160Global = false;
 constexpr int kGp112Grid = 1024, kGp160Grid = 512;
 constexpr size_t kGp112Bytes = kGp112Global ? (size_t)kGp112Grid * gp_store_doubles(112) * 8 : 0;
 constexpr size_t kGp160Bytes = kGp160Global ? (size_t)kGp160Grid * gp_store_doubles(160) * 8 : 0;
 
-template <int NP> struct gp_threads { static constexpr int T = (NP >= 768) ? 1024 : ((NP >= 160) ? 512 : 256); };
-// the two global-scratch tiers whose second pivot panel fits LDS sweep two pivot tiles per pass over the matrix
-template <int NP, bool GLOBAL_K> struct gp_fuse { static constexpr bool F = GLOBAL_K && NP <= 512; };
 template <int NP> struct gp_grid_cap { static constexpr int G = (NP == 112) ? kGp112Grid : ((NP == 160) ? kGp160Grid : ((NP == kGpSmallNP) ? kGpSmallGrid : kGpGlobalGrid)); };
-
-// waves per SIMD to leave room for: the 64- and 112-row tiers fit two or more workgroups per CU in LDS,
-// so their register budget is halved (the L-BFGS-B driver spills a little, the sweep does not)
-template <int NP, bool GLOBAL_K> struct gp_waves { static constexpr int N = (NP <= 64) ? 3 : (GLOBAL_K ? ((NP == 512) ? 2 : 4) : 2); };
-
-// the long-object tier of the 2-D GP: light curves of more than 767 rows, up to kGpLongNP - 1 valid points; Gram matrix AND
-// working set (panels, point arrays, optimiser state) in per-workgroup slabs of global scratch
-constexpr int kGpLongNP = 2048;
 constexpr int kGpLongGrid = 8;
-// (no pivot look-ahead: its staging tile is handed over between lanes of one wavefront under wave-level fences, which the
-//  tiers rely on for LDS only)
-template <int NP> struct gp_working_set { using type = GpLds<NP, gp_threads<NP>::T / 64, false, false, false>; };
 constexpr size_t kGpLongSBytes = (sizeof(gp_working_set<kGpLongNP>::type) + 255) & ~(size_t)255;
 constexpr size_t kGpLongBytes = (size_t)kGpLongGrid * ((size_t)gp_store_doubles(kGpLongNP) * 8 + kGpLongSBytes);
 

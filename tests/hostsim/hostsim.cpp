@@ -46,6 +46,28 @@ static void run_gp(int64_t n_obj, const int64_t* offsets, const double* t, const
     }
 }
 
+// the objective alone (tests/test_gp_eval_cpu.py; the device counterpart is tests/devprobe/gp_probe.hip): m prepared
+// points -- what gp_object leaves in S.t, S.y, S.e2 and hands to S.sm.set_band -- and ne evaluations, evaluation e on the
+// first n_e[e] points at p_e[e][0..4).  f: [ne], g: [ne][4], alpha: [ne][m].  Returns 1 on sizes outside the working set.
+extern "C" int hostsim_gp_eval(int m, const double* t, const uint8_t* band, const double* y, const double* e2, int ne,
+                               const int* n_e, const double* p_e, const uint8_t* need, double* f, double* g, double* alpha) {
+    using W = WaveHost;
+    constexpr int NP = 240;
+    if (m < 1 || m + 1 > NP || ne < 0) return 1;
+    for (int i = 0; i < m; ++i)
+        if (band[i] >= 6) return 1;
+    for (int e = 0; e < ne; ++e)
+        if (n_e[e] < 1 || n_e[e] > m) return 1;
+    auto S = std::make_unique<GpLds<NP, 1>>();
+    std::vector<double> K((size_t)gp_store_doubles(NP));
+    for (int i = 0; i < m; ++i) { S->t[i] = t[i]; S->sm.set_band(i, band[i]); S->y[i] = y[i]; S->e2[i] = e2[i]; }
+    for (int e = 0; e < ne; ++e) {
+        gp_eval<W, NP, double*>(p_e + 4 * e, n_e[e], *S, K.data(), f[e], g + 4 * e, need[e] != 0);
+        for (int i = 0; i < n_e[e]; ++i) alpha[(size_t)e * m + i] = S->alpha[i];
+    }
+    return 0;
+}
+
 extern "C" int hostsim_extract(int set, int64_t n_obj, const int64_t* offsets, const double* t,
                                const double* flux, const double* err, const uint8_t* band,
                                const double* z, double* out, int32_t* status) {
