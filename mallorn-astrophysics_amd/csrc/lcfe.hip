@@ -18,6 +18,7 @@
 #include "../../include/lcfe.h"
 #include "feature_sets.hpp"
 #include "workspace.hpp"
+#include "tickets.hpp"
 #include "stat_lean.hpp"
 #include "stat_lanes.hpp"
 #include "gp1d.hpp"
@@ -108,24 +109,9 @@ int launch_grid(void (*kernel)(P...), int threads, GridCaps caps, int64_t work_i
     return 0;
 }
 
-struct BatchView {
-    const int64_t* offsets;
-    const double* t;
-    const double* f;
-    const double* e;
-    const uint8_t* b;
-    const double* z;
-    int64_t n_obj;
-};
-
 // ---- binning: index lists per LDS tier (feature sets) and per Gram-matrix tier (GP)
-// (the lists, the slots of the counts and tickets and the regions behind them: workspace.hpp)
+// (the lists, the slots of the counts and tickets and the regions behind them: workspace.hpp; BatchView, Bins: tickets.hpp)
 constexpr int kBinThreads = 1024;
-struct Bins {
-    int* lists;                        // [kNumLists][n_obj]: set tiers, GP tiers, statistics fallback
-    int* counts;                       // [kNumLists]
-    int64_t stride;                    // n_obj
-};
 
 // What every launcher of a set gets, built once per set by lcfe_extract_device: the batch and its bins, where the set's
 // columns and status words go, its stream, and its share of the workspace; the launchers are its members.
@@ -204,7 +190,7 @@ __global__ __launch_bounds__(kBinThreads) void bin_kernel(const int64_t* offsets
 #pragma unroll
     for (int g = 0; g < 2; ++g)
         if (bin[g] >= 0) {
-            const int k = g * kNumBins + bin[g];
+            const int k = tier_list(g, bin[g]);
             lists[(int64_t)k * n_obj + base[k] + wcount[wave][k] + rank[g]] = (int)i;
         }
 }
@@ -215,8 +201,8 @@ template <class W>
 __device__ void nan_fill_bins(const Bins& bins, int g, int from, double* out, int ld, int col0, int ncol,
                               int32_t* status, int st_ld, int st0, int nst) {
     for (int b = from; b < kNumBins; ++b) {
-        const int c = bins.counts[g * kNumBins + b];
-        const int* list = bins.lists + (int64_t)(g * kNumBins + b) * bins.stride;
+        const int c = bins.count(tier_list(g, b));
+        const int* list = bins.list(tier_list(g, b));
         for (int pos = blockIdx.x; pos < c; pos += gridDim.x) {
             const int64_t i = list[pos];
             fill_row_nan<W>(out + i * (int64_t)ld + col0, ncol);
@@ -246,42 +232,28 @@ __global__ __launch_bounds__(64, (set_waves<SET, CAP>::N)) void set_kernel(Batch
     using W = WaveDev;
     const int ncol = SetTraits<SET>::ncols;
     const int nst = SetTraits<SET>::nstatus;
-    const int count = bins.counts[bin];
-    const int* list = bins.lists + (int64_t)bin * bins.stride;
+    const int count = bins.count(bin);
+    const int* list = bins.list(bin);
     // a sparsely filled tier hands out smaller tickets, so that every wave gets several of them
-    const int per_wave = count / (4 * (int)gridDim.x);
-    chunk = (per_wave < 1) ? 1 : ((per_wave < chunk) ? per_wave : chunk);
+    chunk = ticket_chunk(count, chunk, 4, 1);
     LCFE_PT_INIT();
     LCFE_PT0();
     for (;;) {
-        if (threadIdx.x == 0) next_ticket = (long long)atomicAdd(ticket, 1ull);
-        __syncthreads();
-        const int64_t base = next_ticket * chunk;
-        __syncthreads();
+        const int64_t base = block_ticket(ticket, next_ticket) * chunk;
         if (base >= count) break;
         const int nk = (count - base < chunk) ? (int)(count - base) : chunk;
-        int obj_l = 0, n_l = 0;
-        long long s_l = 0;
-        if ((int)threadIdx.x < nk) {
-            obj_l = list[base + threadIdx.x];
-            s_l = B.offsets[obj_l];
-            n_l = (int)(B.offsets[obj_l + 1] - s_l);
-        }
+        TicketChunk tc;
+        tc.load(list, base, nk, B);
         for (int k = 0; k < nk; ++k) {
-            const int64_t i = W::rdlane(obj_l, k);
-            const int64_t s = ((int64_t)W::rdlane((int)(s_l >> 32), k) << 32) | (unsigned int)W::rdlane((int)s_l, k);
-            const int n = W::rdlane(n_l, k);
+            const auto [i, s, n] = tc.object(k);
             double* row = out + i * (int64_t)ld + col0;
             int32_t* st = (status && nst) ? status + i * (int64_t)st_ld + st0 : nullptr;
-            ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, n, B.z ? B.z[i] : qnan()};
+            ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n, B.z ? B.z[i] : qnan()};
             LCFE_PT(5);
             const int rc = RunSet<W, SET, CAP>::run(in, ws, row, st);
             if constexpr (SetTraits<SET>::overflow_list >= 0) {
                 // (research: r band longer than the Mexican-hat grid of this tier) the long-object tier takes the light curve
-                if (rc == -100 && threadIdx.x == 0) {
-                    const int slot = atomicAdd(&bins.counts[SetTraits<SET>::overflow_list], 1);
-                    bins.lists[(int64_t)SetTraits<SET>::overflow_list * bins.stride + slot] = (int)i;
-                }
+                if (rc == -100 && threadIdx.x == 0) bins.append(SetTraits<SET>::overflow_list, (int)i);
             }
             (void)rc;
             LCFE_PT0B();
@@ -304,46 +276,32 @@ __global__ __launch_bounds__(64, stat_lean_waves<CAP>::N) void stat_lean_kernel(
     __shared__ StatLeanLds<CAP> L;
     __shared__ long long next_ticket;
     using W = WaveDev;
-    const int count = bins.counts[bin];
-    const int* list = bins.lists + (int64_t)bin * bins.stride;
+    const int count = bins.count(bin);
+    const int* list = bins.list(bin);
     // tickets of at least two light curves: one counter serves about 90 tickets per microsecond, which a statistics
     // tier of 20 000 light curves would otherwise spend more time on than on the light curves
-    const int per_wave = count / (2 * (int)gridDim.x);
-    chunk = (per_wave < 2) ? 2 : ((per_wave < chunk) ? per_wave : chunk);
+    chunk = ticket_chunk(count, chunk, 2, 2);
     LCFE_PT_INIT();
     LCFE_PT0();
     for (;;) {
-        if (threadIdx.x == 0) next_ticket = (long long)atomicAdd(ticket, 1ull);
-        __syncthreads();
-        const int64_t base = next_ticket * chunk;
-        __syncthreads();
+        const int64_t base = block_ticket(ticket, next_ticket) * chunk;
         if (base >= count) break;
         const int nk = (count - base < chunk) ? (int)(count - base) : chunk;
-        int obj_l = 0, n_l = 0;
-        long long s_l = 0;
-        if ((int)threadIdx.x < nk) {
-            obj_l = list[base + threadIdx.x];
-            s_l = B.offsets[obj_l];
-            n_l = (int)(B.offsets[obj_l + 1] - s_l);
-        }
+        TicketChunk tc;
+        tc.load(list, base, nk, B);
         for (int k = 0; k < nk; ++k) {
-            const int obj = W::rdlane(obj_l, k);
-            const int64_t s = ((int64_t)W::rdlane((int)(s_l >> 32), k) << 32) | (unsigned int)W::rdlane((int)s_l, k);
-            const int n = W::rdlane(n_l, k);
-            ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, n, qnan()};
+            const auto [obj, s, n] = tc.object(k);
+            ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n, qnan()};
             LCFE_PT(5);
             const bool lean = stat_lean_stage<CAP>(in, L);
             LCFE_PT(0);
             if (lean) {
-                stat_lean_object<CAP>(n, L);
+                stat_lean_object<CAP>((int)n, L);
                 LCFE_PT0B();
-                store_row<W>(L.out, out + (int64_t)obj * ld + col0, STAT_NCOL);
+                store_row<W>(L.out, out + obj * ld + col0, STAT_NCOL);
                 W::sync();
                 LCFE_PT(3);
-            } else if (threadIdx.x == 0) {
-                const int slot = atomicAdd(&bins.counts[kStatFallbackList], 1);
-                bins.lists[(int64_t)kStatFallbackList * bins.stride + slot] = obj;
-            }
+            } else if (threadIdx.x == 0) bins.append(kStatFallbackList, (int)obj);
         }
     }
     LCFE_PT(5);
@@ -368,24 +326,16 @@ __global__ __launch_bounds__(64) void set_long_kernel(BatchView B, Bins bins, in
     __shared__ long long next_ticket;
     SetLds<SET, kLongCap>& ws = *reinterpret_cast<SetLds<SET, kLongCap>*>(slabs + (size_t)blockIdx.x * long_slab_bytes<SET>());
     const int ncol = SetTraits<SET>::ncols, nst = SetTraits<SET>::nstatus;
-    const int c0 = (l0 >= 0) ? bins.counts[l0] : 0, c1 = (l1 >= 0) ? bins.counts[l1] : 0, c2 = (l2 >= 0) ? bins.counts[l2] : 0;
+    const int c0 = (l0 >= 0) ? bins.count(l0) : 0, c1 = (l1 >= 0) ? bins.count(l1) : 0, c2 = (l2 >= 0) ? bins.count(l2) : 0;
     for (;;) {
-        if (threadIdx.x == 0) next_ticket = (long long)atomicAdd(ticket, 1ull);
-        __syncthreads();
-        const int64_t pos = next_ticket;
-        __syncthreads();
+        const int64_t pos = block_ticket(ticket, next_ticket);
         if (pos >= (int64_t)c0 + c1 + c2) break;
         const int li = (pos < c0) ? l0 : ((pos < (int64_t)c0 + c1) ? l1 : l2);
         const int64_t at = (pos < c0) ? pos : ((pos < (int64_t)c0 + c1) ? pos - c0 : pos - c0 - c1);
-        // (wave-uniform by construction; said explicitly, so that the branch on the length below is a scalar branch --
-        //  as a divergent `continue` the compiler turned it into an inner loop that re-read the same ticket for ever)
-        const int64_t i = __builtin_amdgcn_readfirstlane(bins.lists[(int64_t)li * bins.stride + at]);
-        const int64_t s = B.offsets[i];
-        const int64_t n = B.offsets[i + 1] - s;
+        const auto [i, s, n] = take_object(B, bins.list(li), at);
         double* row = out + i * (int64_t)ld + col0;
         int32_t* st = (status && nst) ? status + i * (int64_t)st_ld + st0 : nullptr;
-        const bool fits = __builtin_amdgcn_readfirstlane((int)(n <= kLongCap)) != 0;
-        if (fits) {
+        if (n <= kLongCap) {
             ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n, B.z ? B.z[i] : qnan()};
             RunSet<W, SET, kLongCap>::run(in, ws, row, st);
         } else {
@@ -439,16 +389,16 @@ constexpr bool stat_route_takes(int list, int n, int eff) {
 // Batch `b`, numbered from route R's first: route R's if its list has that many batches, else the next route's.
 template <int R>
 __device__ __forceinline__ void stat_lanes_route(int b, const int (&count)[kStatLanesRoutes], const BatchView& B, const Bins& bins, LanesBuf lbuf,
-                                                 LanesBuf lall, double* out, int ld, int col0, int* rl, int* rc) {
+                                                 LanesBuf lall, double* out, int ld, int col0, int retry) {
     if constexpr (R < kStatLanesRoutes) {
         constexpr StatLanesRoute r = kStatLanesRoute[R];
         const int nb = (count[R] + r.batch() - 1) / r.batch();
         if (b < nb) {
-            stat_lanes_run<r.lpo, r.cap, r.iters>(B.offsets, B.t, B.f, B.e, B.b, bins.lists + (int64_t)r.list * bins.stride, count[R], b, lbuf,
-                                                  lall, out, ld, col0, rl, rc);
+            stat_lanes_run<r.lpo, r.cap, r.iters>(B.offsets, B.t, B.f, B.e, B.b, bins.list(r.list), count[R], b, lbuf, lall, out, ld, col0, bins,
+                                                  retry);
             return;
         }
-        stat_lanes_route<R + 1>(b - nb, count, B, bins, lbuf, lall, out, ld, col0, rl, rc);
+        stat_lanes_route<R + 1>(b - nb, count, B, bins, lbuf, lall, out, ld, col0, retry);
     }
 }
 #ifdef LCFE_DEBUG
@@ -479,11 +429,10 @@ __global__ __launch_bounds__(64, 2) void stat_lanes_all_kernel(BatchView B, Bins
 #endif
     const LanesBuf lbuf = lanes_buf(L.buf, 64 * StatLanesLds<kStatLanesMaxCap>::STRIDE, bad_p), lall = lanes_buf(L.all_rows, 8 * 17, bad_p);
     static_assert(kStatLanesRoutes == 5, "one count per route");
-    const int count[kStatLanesRoutes] = {bins.counts[kStatLanesRoute[0].list], bins.counts[kStatLanesRoute[1].list],
-                                         bins.counts[kStatLanesRoute[2].list], bins.counts[kStatLanesRoute[3].list],
-                                         bins.counts[kStatLanesRoute[4].list]};
-    stat_lanes_route<0>((int)blockIdx.x, count, B, bins, lbuf, lall, out, ld, col0, bins.lists + (int64_t)retry * bins.stride,
-                        &bins.counts[retry]);
+    const int count[kStatLanesRoutes] = {bins.count(kStatLanesRoute[0].list), bins.count(kStatLanesRoute[1].list),
+                                         bins.count(kStatLanesRoute[2].list), bins.count(kStatLanesRoute[3].list),
+                                         bins.count(kStatLanesRoute[4].list)};
+    stat_lanes_route<0>((int)blockIdx.x, count, B, bins, lbuf, lall, out, ld, col0, retry);
 }
 
 // Which statistics kernel takes a light curve of up to 512 rows: ONE launch over the three tier lists (128 / 256 / 512
@@ -533,7 +482,7 @@ __global__ __launch_bounds__(kPlanThreads) void stat_plan_kernel(BatchView B, Bi
     __shared__ int base[kPlanDst];
     constexpr int PER = kPlanThreads / 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 3, j = lane & 7;
-    const int c0 = bins.counts[0], c1 = bins.counts[1], c2 = bins.counts[2];
+    const int c0 = bins.count(0), c1 = bins.count(1), c2 = bins.count(2);
     const int nb2 = (c2 + PER - 1) / PER, nb1 = (c1 + PER - 1) / PER, nb0 = (c0 + PER - 1) / PER;
     int blk = (int)blockIdx.x, tier, count;
     if (blk < nb2) { tier = 2; count = c2; }
@@ -544,7 +493,7 @@ __global__ __launch_bounds__(kPlanThreads) void stat_plan_kernel(BatchView B, Bi
     int obj = -1, n = 0;
     int64_t s0 = 0;
     if (pos < count) {
-        obj = bins.lists[(int64_t)tier * bins.stride + pos];
+        obj = bins.list(tier)[pos];
         s0 = B.offsets[obj];
         n = (int)(B.offsets[obj + 1] - s0);
     }
@@ -591,10 +540,10 @@ __global__ __launch_bounds__(kPlanThreads) void stat_plan_kernel(BatchView B, Bi
             wcount[w][threadIdx.x] = total;
             total += c;
         }
-        base[threadIdx.x] = total ? atomicAdd(&bins.counts[dst_of((int)threadIdx.x)], total) : 0;
+        base[threadIdx.x] = total ? bins.reserve(dst_of((int)threadIdx.x), total) : 0;
     }
     __syncthreads();
-    if (cls >= 0) bins.lists[(int64_t)dst_of(cls) * bins.stride + base[cls] + wcount[wave][cls] + rank] = obj;
+    if (cls >= 0) bins.list(dst_of(cls))[base[cls] + wcount[wave][cls] + rank] = obj;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -657,15 +606,12 @@ __global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bin
     __shared__ long long next_ticket;
     __shared__ int loc[kFitTiers][64], nloc[kFitTiers], base_of[kFitTiers];
     using W = WaveDev;
-    const int count = bins.counts[bin];
-    const int* list = bins.lists + (int64_t)bin * bins.stride;
-    const int per_wave = count / (4 * (int)gridDim.x);
-    chunk = (per_wave < 1) ? 1 : ((per_wave < chunk) ? per_wave : chunk);
+    const int count = bins.count(bin);
+    const int* list = bins.list(bin);
+    chunk = ticket_chunk(count, chunk, 4, 1);
     for (;;) {
-        if (threadIdx.x == 0) { next_ticket = (long long)atomicAdd(ticket, 1ull); for (int q = 0; q < kFitTiers; ++q) nloc[q] = 0; }
-        __syncthreads();
-        const int64_t base = next_ticket * chunk;
-        __syncthreads();
+        if (threadIdx.x == 0) for (int q = 0; q < kFitTiers; ++q) nloc[q] = 0;
+        const int64_t base = block_ticket(ticket, next_ticket) * chunk;
         if (base >= count) break;
         const int nk = (count - base < chunk) ? (int)(count - base) : chunk;
         for (int k = 0; k < nk; ++k) {
@@ -684,18 +630,12 @@ __global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bin
                 // a band beyond the largest fit tier: the whole object goes to the object-level kernel, which takes
                 // light curves of up to 1024 rows; beyond that the fit is not available (NaN, status -100)
                 if (n <= 1024) {
-                    if (threadIdx.x == 0) {
-                        const int slot = atomicAdd(&bins.counts[kBazinFallbackList], 1);
-                        bins.lists[(int64_t)kBazinFallbackList * bins.stride + slot] = (int)i;
-                    }
+                    if (threadIdx.x == 0) bins.append(kBazinFallbackList, (int)i);
                 } else {
                     // the long-object tier takes it (when the caller's workspace has its slabs); NaN and -100 until then
                     fill_row_nan<W>(out + i * (int64_t)ld + col0, BAZIN_NCOL);
                     if (status && threadIdx.x < 12) status[i * (int64_t)st_ld + st0 + threadIdx.x] = -100;
-                    if (threadIdx.x == 0) {
-                        const int slot = atomicAdd(&bins.counts[kBazinLongList], 1);
-                        bins.lists[(int64_t)kBazinLongList * bins.stride + slot] = (int)i;
-                    }
+                    if (threadIdx.x == 0) bins.append(kBazinLongList, (int)i);
                 }
             } else if (threadIdx.x < 6) {
                 const int b = threadIdx.x;
@@ -858,15 +798,11 @@ __global__ __launch_bounds__(64, 2) void powerlaw_partition_kernel(BatchView B, 
     __shared__ ObjLds<CAP> L;
     __shared__ long long next_ticket;
     using W = WaveDev;
-    const int count = bins.counts[bin];
-    const int* list = bins.lists + (int64_t)bin * bins.stride;
-    const int per_wave = count / (4 * (int)gridDim.x);
-    chunk = (per_wave < 1) ? 1 : ((per_wave < chunk) ? per_wave : chunk);
+    const int count = bins.count(bin);
+    const int* list = bins.list(bin);
+    chunk = ticket_chunk(count, chunk, 4, 1);
     for (;;) {
-        if (threadIdx.x == 0) next_ticket = (long long)atomicAdd(ticket, 1ull);
-        __syncthreads();
-        const int64_t base = next_ticket * chunk;
-        __syncthreads();
+        const int64_t base = block_ticket(ticket, next_ticket) * chunk;
         if (base >= count) break;
         const int nk = (count - base < chunk) ? (int)(count - base) : chunk;
         for (int q = 0; q < nk; ++q) {
@@ -889,17 +825,11 @@ __global__ __launch_bounds__(64, 2) void powerlaw_partition_kernel(BatchView B, 
             if (kmax > kFitCaps[kFitTiers - 1]) {
                 // more post-peak rows than the largest fit tier: object-level kernel (up to 1024 rows), else not available
                 if (n <= 1024) {
-                    if (threadIdx.x == 0) {
-                        const int slot = atomicAdd(&bins.counts[kPowerlawFallbackList], 1);
-                        bins.lists[(int64_t)kPowerlawFallbackList * bins.stride + slot] = (int)i;
-                    }
+                    if (threadIdx.x == 0) bins.append(kPowerlawFallbackList, (int)i);
                 } else {
                     fill_row_nan<W>(out + i * (int64_t)ld + col0, POWERLAW_NCOL);
                     if (status && threadIdx.x < 54) status[i * (int64_t)st_ld + st0 + threadIdx.x] = -100;
-                    if (threadIdx.x == 0) {
-                        const int slot = atomicAdd(&bins.counts[kPowerlawLongList], 1);
-                        bins.lists[(int64_t)kPowerlawLongList * bins.stride + slot] = (int)i;
-                    }
+                    if (threadIdx.x == 0) bins.append(kPowerlawLongList, (int)i);
                 }
             } else if (threadIdx.x < 3) {
                 const int j = threadIdx.x;
@@ -1042,17 +972,12 @@ __global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP, GLOBAL_K>::N)) voi
     __shared__ double Klds[GLOBAL_K ? 1 : gp_store_doubles(NP)];
     __shared__ long long next_ticket;
     double* Kg = kscratch + (size_t)blockIdx.x * (size_t)gp_store_doubles(NP);
-    const int count = bins.counts[kNumBins + bin];
-    const int* list = bins.lists + (int64_t)(kGpSortedList + bin) * bins.stride;      // longest first (gp_sort_kernel)
+    const int count = bins.count(gp_list(bin));
+    const int* list = bins.list(gp_sorted_list(bin));      // longest first (gp_sort_kernel)
     for (;;) {
-        if (threadIdx.x == 0) next_ticket = (long long)atomicAdd(ticket, 1ull);
-        __syncthreads();
-        const int64_t pos = next_ticket;
-        __syncthreads();
+        const int64_t pos = block_ticket(ticket, next_ticket);
         if (pos >= count) break;
-        const int64_t i = list[pos];
-        const int64_t s = B.offsets[i];
-        const int64_t n64 = B.offsets[i + 1] - s;
+        const auto [i, s, n64] = take_object(B, list, pos);
         double* row = out + i * (int64_t)ld + col0;
         int32_t* st = status ? status + i * (int64_t)st_ld + st0 : nullptr;
         ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n64, qnan()};
@@ -1079,17 +1004,12 @@ __global__ __launch_bounds__(gp_threads<kGpLongNP>::T, 1) void gp_long_kernel(Ba
     __shared__ long long next_ticket;
     double* Kg = reinterpret_cast<double*>(slabs) + (size_t)blockIdx.x * (size_t)gp_store_doubles(NP);
     SL& S = *reinterpret_cast<SL*>(slabs + (size_t)kGpLongGrid * gp_store_doubles(NP) * 8 + (size_t)blockIdx.x * kGpLongSBytes);
-    const int count = bins.counts[kNumBins + bin];
-    const int* list = bins.lists + (int64_t)(kNumBins + bin) * bins.stride;
+    const int count = bins.count(gp_list(bin));
+    const int* list = bins.list(gp_list(bin));
     for (;;) {
-        if (threadIdx.x == 0) next_ticket = (long long)atomicAdd(ticket, 1ull);
-        __syncthreads();
-        const int64_t pos = next_ticket;
-        __syncthreads();
+        const int64_t pos = block_ticket(ticket, next_ticket);
         if (pos >= count) break;
-        const int64_t i = list[pos];
-        const int64_t s = B.offsets[i];
-        const int64_t n64 = B.offsets[i + 1] - s;
+        const auto [i, s, n64] = take_object(B, list, pos);
         int32_t* st = status ? status + i * (int64_t)st_ld + st0 : nullptr;
         ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n64, qnan()};
         gp_object<W, NP>(in, S, [&](const double* x, int n, double& f, double* g, bool need) {
@@ -1108,9 +1028,9 @@ constexpr int kGpSortThreads = 1024;
 __global__ __launch_bounds__(kGpSortThreads) void gp_sort_kernel(const int64_t* offsets, Bins bins) {
     const int tier = blockIdx.x;
     const int hi = (tier == 0) ? 63 : (tier == 1) ? 111 : (tier == 2) ? 159 : (tier == 3) ? kGpSmallNP - 1 : (tier == 4) ? kGpMidNP - 1 : kGpGlobalNP - 1;
-    const int count = bins.counts[kNumBins + tier];
-    const int* src = bins.lists + (int64_t)(kNumBins + tier) * bins.stride;
-    int* dst = bins.lists + (int64_t)(kGpSortedList + tier) * bins.stride;
+    const int count = bins.count(gp_list(tier));
+    const int* src = bins.list(gp_list(tier));
+    int* dst = bins.list(gp_sorted_list(tier));
     __shared__ int hist[1024], wsum[kGpSortThreads / 64];
     hist[threadIdx.x] = 0;
     __syncthreads();
@@ -1268,17 +1188,14 @@ __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int
     __shared__ int boff[5], nvalid[4];
     __shared__ int wcnt[T / 64][4];
     __shared__ long long next_ticket;
-    const int count = bins.counts[kNumBins + bin];
-    const int* list = bins.lists + (int64_t)(kNumBins + bin) * bins.stride;
+    const int count = bins.count(gp_list(bin));
+    const int* list = bins.list(gp_list(bin));
     for (;;) {
-        if (threadIdx.x == 0) next_ticket = (long long)atomicAdd(ticket, 1ull);
-        __syncthreads();
-        const int64_t pos = next_ticket;
-        __syncthreads();
+        const int64_t pos = block_ticket(ticket, next_ticket);
         if (pos >= count) break;
-        const int64_t i = list[pos];
-        const int64_t s = B.offsets[i];
-        const int n = (int)(B.offsets[i + 1] - s);
+        const ListObject o = take_object(B, list, pos);
+        const int64_t i = o.i, s = o.s;
+        const int n = (int)o.n;
         const double* t = B.t + s;
         const double* f = B.f + s;
         const double* e = B.e + s;
@@ -1437,20 +1354,14 @@ __global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B,
     double* Kg = reinterpret_cast<double*>(slabs) + (size_t)blockIdx.x * (size_t)gp_store_doubles(NP);
     Gp1dLongTierWs& S = *reinterpret_cast<Gp1dLongTierWs*>(slabs + (size_t)kGp1dLongTierGrid * gp_store_doubles(NP) * 8 +
                                                          (size_t)blockIdx.x * kGp1dLongTierSBytes);
-    const int count = bins.counts[kNumBins + 6];
-    const int* list = bins.lists + (int64_t)(kNumBins + 6) * bins.stride;
+    const int count = bins.count(kGpLongList);
+    const int* list = bins.list(kGpLongList);
     for (;;) {
-        if (threadIdx.x == 0) next_ticket = (long long)atomicAdd(ticket, 1ull);
-        __syncthreads();
-        const int64_t pos = next_ticket;
-        __syncthreads();
+        const int64_t pos = block_ticket(ticket, next_ticket);
         if (pos >= count) break;
-        // (uniform by construction; said explicitly, so that the branches on the length and the loops over the rows are
-        //  scalar -- DESIGN §3: a per-lane length once turned the ticket loop into an endless re-read of one ticket)
-        const int64_t i = __builtin_amdgcn_readfirstlane(list[pos]);
-        const int64_t s = B.offsets[i];
-        const int64_t n64 = B.offsets[i + 1] - s;
-        const int n = __builtin_amdgcn_readfirstlane((int)((n64 > kLongCap) ? kLongCap + 1 : n64));
+        const ListObject o = take_object(B, list, pos);
+        const int64_t i = o.i, s = o.s;
+        const int n = (int)((o.n > kLongCap) ? kLongCap + 1 : o.n);
         if (n <= kLongCap) {
             const double* t = B.t + s;
             const double* f = B.f + s;

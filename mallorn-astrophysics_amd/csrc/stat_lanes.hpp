@@ -387,14 +387,14 @@ __device__ __forceinline__ void lanes_merge_levels(double (&w)[CAP], LanesBuf bu
 }
 
 // 64 / LPO light curves (one per LPO-lane group: `obj` < 0 = none; CSR rows [s1, e1)) -> their 123 columns, or list
-// `fallback_list`.  ITERS = rows / LPO a light curve of the list may have (band code 256 = no row -- 255 is a code a file
-// may hold).  The rows are loaded in predicated blocks of four trips: one basic block of unconditional loads, a
+// `fallback` of `lists` (Bins of tickets.hpp: lists.append(fallback, obj)).  ITERS = rows / LPO a light curve of the list
+// may have (band code 256 = no row -- 255 is a code a file may hold).  The rows are loaded in predicated blocks of four trips: one basic block of unconditional loads, a
 // persistent batch loop around this function, or exec-masked element loops all made the compiler spill hundreds of
 // registers (profiles/r02_stat_instruction_budget.md).
-template <int LPO, int CAP, int ITERS>
+template <int LPO, int CAP, int ITERS, class Lists>
 __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double* gf, const double* ge, const uint8_t* gb, int obj,
                                                  int64_t s1, int64_t e1, LanesBuf buf, LanesBuf all_rows, double* out, int ld, int col0,
-                                                 int* fallback_list, int* fallback_count) {
+                                                 const Lists& lists, int fallback) {
     using L = LanesLayout<LPO>;
     using G = typename L::G;
     constexpr int STRIDE = StatLanesLds<CAP>::STRIDE;
@@ -806,18 +806,15 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
             if (lane + 64 < STAT_NCOL) row[lane + 64] = src[lane + 64];
         }
     }
-    if (!done && has_obj && j == 0) {
-        const int slot = atomicAdd(fallback_count, 1);
-        fallback_list[slot] = obj;
-    }
+    if (!done && has_obj && j == 0) lists.append(fallback, obj);
     G::sync();
 }
 
 // One workgroup = one batch (`batch`) of 64 / LPO consecutive list entries; `buf`: 64 x (CAP + 1) doubles of LDS.
-template <int LPO, int CAP, int ITERS>
+template <int LPO, int CAP, int ITERS, class Lists>
 __device__ __forceinline__ void stat_lanes_run(const int64_t* offsets, const double* gt, const double* gf, const double* ge,
                                                const uint8_t* gb, const int* list, int count, int batch, LanesBuf buf, LanesBuf all_rows,
-                                               double* out, int ld, int col0, int* fallback_list, int* fallback_count) {
+                                               double* out, int ld, int col0, const Lists& lists, int fallback) {
     const int g = (threadIdx.x & 63) / LPO;
     const int64_t base = (int64_t)batch * (64 / LPO);
     int obj = -1;
@@ -827,7 +824,7 @@ __device__ __forceinline__ void stat_lanes_run(const int64_t* offsets, const dou
         s1 = offsets[obj];
         e1 = offsets[obj + 1];
     }
-    stat_lanes_batch<LPO, CAP, ITERS>(gt, gf, ge, gb, obj, s1, e1, buf, all_rows, out, ld, col0, fallback_list, fallback_count);
+    stat_lanes_batch<LPO, CAP, ITERS>(gt, gf, ge, gb, obj, s1, e1, buf, all_rows, out, ld, col0, lists, fallback);
 }
 
 }  // namespace lcfe

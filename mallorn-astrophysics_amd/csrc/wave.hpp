@@ -392,6 +392,7 @@ LCFE_FN int uniform_int(int v) {
     return v;
 #endif
 }
+LCFE_FN int64_t uniform_i64(int64_t v) { return ((int64_t)uniform_int((int)(v >> 32)) << 32) | (unsigned int)uniform_int((int)v); }
 
 // quiet NaN without relying on host/device library differences
 LCFE_FN double qnan() { return __builtin_nan(""); }

@@ -25,6 +25,11 @@ constexpr int kPowerlawLongList = 2 * kNumBins + 10;  // ... with more post-peak
 constexpr int kResearchLongList = 2 * kNumBins + 11;  // light curves whose r band spans more days than the Mexican-hat grid in LDS
 static_assert(SetTraits<SET_RESEARCH>::overflow_list == kResearchLongList, "the research set's overflow list");
 constexpr int kGpSortedList = 2 * kNumBins + 12;      // + tier (0..5): the 2-D GP tier's light curves, longest first (gp_sort_kernel)
+// the tier lists by name: group 0 = the LDS tiers of the feature sets (the list's id is its bin), group 1 = the GP tiers
+constexpr int tier_list(int group, int bin) { return group * kNumBins + bin; }
+constexpr int gp_list(int tier) { return tier_list(1, tier); }
+constexpr int gp_sorted_list(int tier) { return kGpSortedList + tier; }
+constexpr int kGpLongList = gp_list(kNumBins - 1);    // light curves beyond the largest Gram-matrix tier
 
 // ---- header: [0, 1024) ticket counters (8 per set up to the extension set, then the fit lists'), [1024, 2048) counts (the
 // lists' lengths, then the fit lists'), [2048, 2304) ticket counters of the registered sets (8 per set)

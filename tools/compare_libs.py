@@ -2,7 +2,8 @@
 usage: compare_libs.py SETS N_OBJ SEED LIB_A LIB_B [ROWS]
 SETS: one set or a comma-separated list run in ONE call ("all": every set of the registry).  ROWS: a comma-separated
 list of row counts; the batch is then one hand-made light curve per count (synth.from_objects, as the tier tests build
-theirs, seeded with SEED) instead of synth.make_lightcurves(N_OBJ, SEED)."""
+theirs, seeded with SEED) instead of synth.make_lightcurves(N_OBJ, SEED).  A count written ROWS@BAND puts every row of that
+light curve into band BAND (0..5) instead of spreading them over the six: a band beyond the fit tiers in a short light curve."""
 import os
 import subprocess
 import sys
@@ -42,10 +43,12 @@ else:
     if len(sys.argv) > 6:
         rng = np.random.default_rng(int(seed))
         objs = []
-        for rows in (int(r) for r in sys.argv[6].split(",")):
+        for spec in sys.argv[6].split(","):
+            rows, _, band = spec.partition("@")
+            rows = int(rows)
             t = np.sort(59000 + rng.uniform(0, 800, rows))
             f = 30 * np.exp(-0.5 * ((t - 59300) / 40) ** 2) + rng.normal(0, 1, rows)
-            objs.append((t, f, np.full(rows, 1.0), rng.choice(6, rows)))
+            objs.append((t, f, np.full(rows, 1.0), np.full(rows, int(band)) if band else rng.choice(6, rows)))
         lc = synth.from_objects(objs)
     else:
         lc = synth.make_lightcurves(int(n), seed=int(seed))
