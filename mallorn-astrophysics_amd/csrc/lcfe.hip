@@ -22,6 +22,7 @@
 #include "stat_lean.hpp"
 #include "stat_lanes.hpp"
 #include "gp1d.hpp"
+#include "gp1d_rows.hpp"
 #include "gp_tiers.hpp"
 #include "augment.hpp"
 #include "sequence.hpp"
@@ -1173,6 +1174,18 @@ struct Gp1dBlockLds {
     double K[gp_store_doubles(NP)];
 };
 
+// The fit of band j (0..3 = g, r, i, z) on policy P: R holds the band's valid rows of the slice (t, f, e) in time order
+// (gp1d_rows.hpp); the working set S and the NP-row matrix K (lds_double* or global_double*) are the caller's.  The band's
+// four values go to orow[4 j ..), its status word to st[j].
+template <class P, int NP, class Rows, class KP, bool IN_LDS>
+__device__ __forceinline__ void gp1d_fit_band(const Rows& R, int j, const double* t, const double* f, const double* e,
+                                              Gp1dLds<NP, P::NWAVES, IN_LDS>& S, KP K, double* orow, int32_t* st) {
+    const int b0 = R.boff[j], m = R.boff[j + 1] - b0;
+    gp1d_band<P, NP>([&](int r, double& tt, double& ff, double& ee) { const int k = R.rows[b0 + r]; tt = t[k]; ff = f[k]; ee = e[k]; }, m, S,
+                     [&](const double* x, int nn, double& fv, double* gv) { gp1d_eval<P, NP, KP>(x, nn, S, K, fv, gv); },
+                     orow + 4 * j, st ? st + j : nullptr);
+}
+
 // MW = waves per SIMD the register allocation leaves room for (= workgroups per CU at 256 threads)
 template <int NP, int ROWCAP, int T, int WNP, int MW>
 __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int bin, int nan_from, double* out, int ld,
@@ -1183,10 +1196,8 @@ __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int
     constexpr size_t kBlockBytes = sizeof(Gp1dBlockLds<NP, W::NWAVES>), kWaveBytes = kWavePath ? 4 * sizeof(Gp1dWaveLds<WNP>) : 0;
     __shared__ __attribute__((aligned(16))) unsigned char raw[(kBlockBytes > kWaveBytes) ? kBlockBytes : kWaveBytes];
     auto& LB = *reinterpret_cast<Gp1dBlockLds<NP, W::NWAVES>*>(raw);
-    __shared__ unsigned short rows[ROWCAP], rows2[ROWCAP];
+    __shared__ Gp1dRows<T, ROWCAP, ROWCAP> R;
     __shared__ double orow[GP1D_NCOL + 3];
-    __shared__ int boff[5], nvalid[4];
-    __shared__ int wcnt[T / 64][4];
     __shared__ long long next_ticket;
     const int count = bins.count(gp_list(bin));
     const int* list = bins.list(gp_list(bin));
@@ -1195,98 +1206,30 @@ __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int
         if (pos >= count) break;
         const ListObject o = take_object(B, list, pos);
         const int64_t i = o.i, s = o.s;
-        const int n = (int)o.n;
         const double* t = B.t + s;
         const double* f = B.f + s;
         const double* e = B.e + s;
-        const uint8_t* bb = B.b + s;
         int32_t* st = status ? status + i * (int64_t)st_ld + st0 : nullptr;
-        // ---- rows of the bands g, r, i, z as one index list partitioned by band, each part in time order
-        int cnt[4] = {0, 0, 0, 0}, nv[4] = {0, 0, 0, 0};
-        for (int k = threadIdx.x; k < n; k += T) {
-            const int band = bb[k];
-            if (band < 1 || band > 4) continue;
-            ++cnt[band - 1];
-            if (!is_nan(f[k]) && !is_nan(e[k]) && e[k] > 0) ++nv[band - 1];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { cnt[j] = W::sum(cnt[j]); nv[j] = W::sum(nv[j]); }
-        if (threadIdx.x == 0) {
-            boff[0] = 0;
-            for (int j = 0; j < 4; ++j) { boff[j + 1] = boff[j] + cnt[j]; nvalid[j] = nv[j]; }
-        }
-        __syncthreads();
-        // stable partition by band: ballot ranks inside a wavefront, wave totals through LDS, running totals per chunk
-        // (one pass over the band bytes instead of one scan of all earlier rows per row)
-        {
-            int run[4] = {0, 0, 0, 0};
-            for (int base = 0; base < n; base += T) {
-                const int k = base + (int)threadIdx.x;
-                const int band = (k < n) ? (int)bb[k] : 0;
-                int rank = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned long long mk = __ballot(band == j + 1);
-                    if (band == j + 1) rank = WaveDev::prefix(mk);
-                    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6][j] = popcll(mk);
-                }
-                __syncthreads();
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    int before = 0, total = 0;
-                    for (int wv = 0; wv < T / 64; ++wv) { const int c = wcnt[wv][j]; total += c; before += (wv < (int)(threadIdx.x >> 6)) ? c : 0; }
-                    if (band == j + 1) rows[boff[j] + run[j] + before + rank] = (unsigned short)k;
-                    run[j] += total;
-                }
-                __syncthreads();
-            }
-        }
-        bool ordered = true;
-        for (int k = threadIdx.x; k + 1 < n; k += T) ordered = ordered && (t[k] <= t[k + 1]);
-        if (!W::all(ordered)) {
-            // stable rank sort of every band part by (time, file index), as the oracle's ``band_sorted``
-            for (int j = 0; j < 4; ++j) {
-                const int b0 = boff[j], m = boff[j + 1] - b0;
-                for (int k = threadIdx.x; k < m; k += T) {
-                    const double tk = t[rows[b0 + k]];
-                    int r = 0;
-                    for (int q = 0; q < m; ++q) {
-                        const double tq = t[rows[b0 + q]];
-                        r += (tq < tk || (tq == tk && q < k)) ? 1 : 0;
-                    }
-                    rows2[b0 + r] = rows[b0 + k];
-                }
-            }
-            __syncthreads();
-            for (int k = threadIdx.x; k < boff[4]; k += T) rows[k] = rows2[k];
-            __syncthreads();
-        }
+        R.build(t, f, e, B.b + s, (int)o.n);
+        auto nvalid = [&](int j) { return R.boff[j + 1] - R.boff[j]; };
         bool fitted[4];
         int most = 0;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { fitted[j] = (boff[j + 1] - boff[j]) >= 5; most = (nvalid[j] > most) ? nvalid[j] : most; }
+        for (int j = 0; j < 4; ++j) { fitted[j] = R.nall[j] >= 5; most = (nvalid(j) > most) ? nvalid(j) : most; }
         // phase 1: every band that fits a WNP-row matrix, one per wavefront, side by side
         if constexpr (kWavePath) {
             const int j = threadIdx.x >> 6;
-            if (nvalid[j] + 1 <= WNP) {
+            if (nvalid(j) + 1 <= WNP) {
                 auto& LW = reinterpret_cast<Gp1dWaveLds<WNP>*>(raw)[j];
-                const int b0 = boff[j], m = boff[j + 1] - b0;
-                gp1d_band<WaveOfBlock, WNP>(
-                    [&](int r, double& tt, double& ff, double& ee) { const int k = rows[b0 + r]; tt = t[k]; ff = f[k]; ee = e[k]; }, m, LW.S,
-                    [&](const double* x, int nn, double& fv, double* gv) { gp1d_eval<WaveOfBlock, WNP, lds_double*>(x, nn, LW.S, (lds_double*)LW.K, fv, gv); },
-                    orow + 4 * j, st ? st + j : nullptr);
+                gp1d_fit_band<WaveOfBlock, WNP>(R, j, t, f, e, LW.S, (lds_double*)LW.K, orow, st);
             }
             __syncthreads();
         }
         // phase 2: the longer bands one after the other on the whole workgroup (same LDS buffer, NP-row matrix)
         if (!kWavePath || most + 1 > WNP) {
             for (int j = 0; j < 4; ++j) {
-                if (kWavePath && nvalid[j] + 1 <= WNP) continue;
-                const int b0 = boff[j], m = boff[j + 1] - b0;
-                gp1d_band<W, NP>([&](int r, double& tt, double& ff, double& ee) { const int k = rows[b0 + r]; tt = t[k]; ff = f[k]; ee = e[k]; },
-                                 m, LB.S,
-                                 [&](const double* x, int nn, double& fv, double* gv) { gp1d_eval<W, NP, lds_double*>(x, nn, LB.S, (lds_double*)LB.K, fv, gv); },
-                                 orow + 4 * j, st ? st + j : nullptr);
+                if (kWavePath && nvalid(j) + 1 <= WNP) continue;
+                gp1d_fit_band<W, NP>(R, j, t, f, e, LB.S, (lds_double*)LB.K, orow, st);
                 __syncthreads();
             }
         }
@@ -1298,12 +1241,8 @@ __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int
                 auto& LG = *reinterpret_cast<Gp1dLds<kGp1dLongNP, W::NWAVES>*>(raw);
                 double* Kg = kslab + (size_t)blockIdx.x * (size_t)gp_store_doubles(kGp1dLongNP);
                 for (int j = 0; j < 4; ++j) {
-                    if (nvalid[j] + 1 <= NP) continue;
-                    const int b0 = boff[j], m = boff[j + 1] - b0;
-                    gp1d_band<W, kGp1dLongNP>([&](int r, double& tt, double& ff, double& ee) { const int k = rows[b0 + r]; tt = t[k]; ff = f[k]; ee = e[k]; },
-                                              m, LG,
-                                              [&](const double* x, int nn, double& fv, double* gv) { gp1d_eval<W, kGp1dLongNP, global_double*>(x, nn, LG, (global_double*)Kg, fv, gv); },
-                                              orow + 4 * j, st ? st + j : nullptr);
+                    if (nvalid(j) + 1 <= NP) continue;
+                    gp1d_fit_band<W, kGp1dLongNP>(R, j, t, f, e, LG, (global_double*)Kg, orow, st);
                     __syncthreads();
                 }
             }
@@ -1345,11 +1284,9 @@ __global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B,
                                                                    int st_ld, int st0, char* slabs, unsigned long long* ticket) {
     constexpr int T = kGp1dThreads, NP = kGp1dLongTierNP;
     using W = BlockDev<T>;
-    __shared__ unsigned short rows[kLongCap];          // valid rows of g, r, i, z, partitioned by band, each part in time order
-    __shared__ unsigned short rows2[NP];               // rank sort of one band (bands of at most NP - 1 valid points only)
+    // valid rows of g, r, i, z, partitioned by band, each part in time order; the rank sort takes the bands the fit takes
+    __shared__ Gp1dRows<T, kLongCap, NP - 1> R;
     __shared__ double orow[GP1D_NCOL + 3];
-    __shared__ int boff[5], nall[4];
-    __shared__ int wcnt[T / 64][4];
     __shared__ long long next_ticket;
     double* Kg = reinterpret_cast<double*>(slabs) + (size_t)blockIdx.x * (size_t)gp_store_doubles(NP);
     Gp1dLongTierWs& S = *reinterpret_cast<Gp1dLongTierWs*>(slabs + (size_t)kGp1dLongTierGrid * gp_store_doubles(NP) * 8 +
@@ -1361,88 +1298,17 @@ __global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B,
         if (pos >= count) break;
         const ListObject o = take_object(B, list, pos);
         const int64_t i = o.i, s = o.s;
-        const int n = (int)((o.n > kLongCap) ? kLongCap + 1 : o.n);
-        if (n <= kLongCap) {
+        if (o.n <= kLongCap) {
             const double* t = B.t + s;
             const double* f = B.f + s;
             const double* e = B.e + s;
-            const uint8_t* bb = B.b + s;
             int32_t* st = status ? status + i * (int64_t)st_ld + st0 : nullptr;
-            auto valid = [&](int k) { return !is_nan(f[k]) && !is_nan(e[k]) && e[k] > 0; };
-            // ---- rows per band (the cross-band columns take a band with >= 5 rows) and VALID rows per band
-            int cnt[4] = {0, 0, 0, 0}, nv[4] = {0, 0, 0, 0};
-            for (int k = threadIdx.x; k < n; k += T) {
-                const int band = bb[k];
-                if (band < 1 || band > 4) continue;
-                ++cnt[band - 1];
-                if (valid(k)) ++nv[band - 1];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { cnt[j] = W::sum(cnt[j]); nv[j] = W::sum(nv[j]); }
-            if (threadIdx.x == 0) {
-                boff[0] = 0;
-                for (int j = 0; j < 4; ++j) { boff[j + 1] = boff[j] + nv[j]; nall[j] = cnt[j]; }
-            }
-            __syncthreads();
-            // stable partition of the valid rows by band (gp1d_kernel's ballot ranks): one pass, O(n) per object
-            {
-                int run[4] = {0, 0, 0, 0};
-                for (int base = 0; base < n; base += T) {
-                    const int k = base + (int)threadIdx.x;
-                    const int band = (k < n && valid(k)) ? (int)bb[k] : 0;
-                    int rank = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const unsigned long long mk = __ballot(band == j + 1);
-                        if (band == j + 1) rank = WaveDev::prefix(mk);
-                        if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6][j] = popcll(mk);
-                    }
-                    __syncthreads();
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        int before = 0, total = 0;
-                        for (int wv = 0; wv < T / 64; ++wv) { const int c = wcnt[wv][j]; total += c; before += (wv < (int)(threadIdx.x >> 6)) ? c : 0; }
-                        if (band == j + 1) rows[boff[j] + run[j] + before + rank] = (unsigned short)k;
-                        run[j] += total;
-                    }
-                    __syncthreads();
-                }
-            }
-            bool ordered = true;
-            for (int k = threadIdx.x; k + 1 < n; k += T) ordered = ordered && (t[k] <= t[k + 1]);
-            if (!W::all(ordered)) {
-                // stable rank sort of every band part by (time, file index), as the oracle's ``band_sorted`` (a NaN time
-                // last, so that the ranks are a permutation whatever the input).  Only bands the fit takes: at most
-                // NP - 1 = 2047 valid points, i.e. at most 2047^2 / 256 = 16 k comparisons per thread and band.
-                for (int j = 0; j < 4; ++j) {
-                    const int b0 = boff[j], m = boff[j + 1] - b0;
-                    if (m + 1 > NP) continue;
-                    for (int k = threadIdx.x; k < m; k += T) {
-                        const double tk = t[rows[b0 + k]];
-                        const bool nk = is_nan(tk);
-                        int r = 0;
-                        for (int q = 0; q < m; ++q) {
-                            const double tq = t[rows[b0 + q]];
-                            const bool nq = is_nan(tq);
-                            const bool lt = (nq == nk) ? (nk ? q < k : (tq < tk || (tq == tk && q < k))) : nk;
-                            r += lt ? 1 : 0;
-                        }
-                        rows2[r] = rows[b0 + k];
-                    }
-                    __syncthreads();
-                    for (int k = threadIdx.x; k < m; k += T) rows[b0 + k] = rows2[k];
-                    __syncthreads();
-                }
-            }
+            R.build(t, f, e, B.b + s, (int)o.n);
             bool fitted[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) fitted[j] = nall[j] >= 5;
+            for (int j = 0; j < 4; ++j) fitted[j] = R.nall[j] >= 5;
             for (int j = 0; j < 4; ++j) {
-                const int b0 = boff[j], m = boff[j + 1] - b0;
-                gp1d_band<W, NP, true>([&](int r, double& tt, double& ff, double& ee) { const int k = rows[b0 + r]; tt = t[k]; ff = f[k]; ee = e[k]; },
-                                       m, S,
-                                       [&](const double* x, int nn, double& fv, double* gv) { gp1d_eval<W, NP, global_double*>(x, nn, S, (global_double*)Kg, fv, gv); },
-                                       orow + 4 * j, st ? st + j : nullptr);
+                gp1d_fit_band<W, NP>(R, j, t, f, e, S, (global_double*)Kg, orow, st);
                 __syncthreads();
             }
             if (threadIdx.x == 0) gp1d_cross_band(orow, fitted);

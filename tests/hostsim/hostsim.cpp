@@ -105,7 +105,11 @@ extern "C" int hostsim_gp1d(int64_t n_obj, const int64_t* offsets, const double*
             const int b = j + 1;                                   // g, r, i, z
             const int bs = obj->boff[b], m = obj->boff[b + 1] - bs;
             fitted[j] = m >= 5;
-            gp1d_band<W, NP>([&](int r, double& tt, double& ff, double& ee) { tt = obj->bt[bs + r]; ff = obj->bf[bs + r]; ee = obj->be[bs + r]; }, m, *ws,
+            // gp1d_band takes the band's valid rows only (on the device: csrc/gp1d_rows.hpp)
+            std::vector<double> vt, vf, ve;
+            for (int r = bs; r < bs + m; ++r)
+                if (!is_nan(obj->bf[r]) && !is_nan(obj->be[r]) && obj->be[r] > 0) { vt.push_back(obj->bt[r]); vf.push_back(obj->bf[r]); ve.push_back(obj->be[r]); }
+            gp1d_band<W, NP>([&](int r, double& tt, double& ff, double& ee) { tt = vt[r]; ff = vf[r]; ee = ve[r]; }, (int)vt.size(), *ws,
                              [&](const double* x, int nn, double& f, double* g) { gp1d_eval<W, NP, double*>(x, nn, *ws, K.data(), f, g); },
                              o + 4 * j, status ? status + i * GP1D_NSTATUS + j : nullptr);
         }
