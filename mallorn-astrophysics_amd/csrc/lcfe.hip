@@ -24,6 +24,7 @@
 #include "gp1d.hpp"
 #include "gp1d_rows.hpp"
 #include "gp_tiers.hpp"
+#include "gp1d_tiers.hpp"
 #include "augment.hpp"
 #include "sequence.hpp"
 
@@ -1153,27 +1154,6 @@ int SetLaunch::launch_gp(const hipStream_t* gs, int ngs, double* const* kslab) c
     return 0;
 }
 
-constexpr int kGp1dLongNP = 768;        // rows of the global-scratch matrix of a long band (160..767 valid points)
-constexpr int kGp1dLongGrid = 256;
-constexpr size_t kGp1dLongBytes = (size_t)kGp1dLongGrid * gp_store_doubles(kGp1dLongNP) * 8;
-constexpr int kGp1dThreads = 256;       // measured: 64 threads 10.1 s, 128: 7.2 s, 256: 6.8 s per 125 k objects
-// ---- per-band 1-D GP (gp1d.hpp): one light curve per workgroup of kGp1dThreads threads, its bands g, r, i, z one after
-// the other; the band's rows are an index list into the CSR slice (time order: file order when the rows
-// are sorted, a rank sort otherwise); NP - 1 = most valid points of a band, ROWCAP = most rows of the object
-// Bands of at most WNP - 1 valid points (the common case) are fitted by the four wavefronts of the workgroup
-// side by side, each on a WNP-row matrix of its own with wave-level fences only; otherwise the bands run one
-// after the other on the whole workgroup with the NP-row matrix.  Both layouts share one LDS buffer.
-template <int WNP>
-struct Gp1dWaveLds {
-    Gp1dLds<WNP, 1> S;
-    double K[gp_store_doubles(WNP)];
-};
-template <int NP, int NW>
-struct Gp1dBlockLds {
-    Gp1dLds<NP, NW> S;
-    double K[gp_store_doubles(NP)];
-};
-
 // The fit of band j (0..3 = g, r, i, z) on policy P: R holds the band's valid rows of the slice (t, f, e) in time order
 // (gp1d_rows.hpp); the working set S and the NP-row matrix K (lds_double* or global_double*) are the caller's.  The band's
 // four values go to orow[4 j ..), its status word to st[j].
@@ -1193,8 +1173,7 @@ __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int
                                                    unsigned long long* ticket, double* kslab) {
     using W = BlockDev<T>;
     constexpr bool kWavePath = (T == 256);
-    constexpr size_t kBlockBytes = sizeof(Gp1dBlockLds<NP, W::NWAVES>), kWaveBytes = kWavePath ? 4 * sizeof(Gp1dWaveLds<WNP>) : 0;
-    __shared__ __attribute__((aligned(16))) unsigned char raw[(kBlockBytes > kWaveBytes) ? kBlockBytes : kWaveBytes];
+    __shared__ __attribute__((aligned(16))) unsigned char raw[gp1d_lds_bytes<NP, T, WNP>()];
     auto& LB = *reinterpret_cast<Gp1dBlockLds<NP, W::NWAVES>*>(raw);
     __shared__ Gp1dRows<T, ROWCAP, ROWCAP> R;
     __shared__ double orow[GP1D_NCOL + 3];
@@ -1263,21 +1242,7 @@ int SetLaunch::gp1d_tier(int ti, int nan_from, double* kslab) const {
                        ld, col0, status, st_ld, st0, tickets + SET_GP1D * 8 + ti, kslab);
 }
 
-// ---- the long-object tier of the per-band GP: light curves of more than 767 rows (GP bin 6), up to kLongCap rows, each band
-// up to kGp1dLongTierNP - 1 valid points -- the 2-D GP's limits.  One light curve per workgroup of kGp1dThreads threads, its
-// bands one after the other on the whole workgroup, persistent over bin 6 through one ticket counter.  The Gram matrix
-// (gp_store_doubles(2048) doubles, 16.9 MB) AND the working set (Gp1dLds<2048, 4> in global scratch, 366 KB) sit in a
-// per-workgroup slab; LDS holds the row lists only: 32 KiB of valid row indices partitioned by band + 4 KiB for the rank
-// sort of one band + < 1 KiB of counters = 37 KiB of the 160 KiB.
-// Grid: 8 workgroups (the 2-D GP's long tier has 8 too): 8 slabs are 138 MB of workspace, 16 would be 276 MB for a tier
-// that sees a handful of light curves per batch.  Tickets are served in file order: ordering them longest first would need
-// another n_obj-entry index list in every workspace (the one bin-6 list is read by the 2-D GP's long kernel at the same time).
-constexpr int kGp1dLongTierNP = kGpLongNP;
-constexpr int kGp1dLongTierGrid = 8;
-using Gp1dLongTierWs = Gp1dLds<kGp1dLongTierNP, kGp1dThreads / 64, false>;
-constexpr size_t kGp1dLongTierSBytes = (sizeof(Gp1dLongTierWs) + 255) & ~(size_t)255;
-constexpr size_t kGp1dLongTierBytes = (size_t)kGp1dLongTierGrid * ((size_t)gp_store_doubles(kGp1dLongTierNP) * 8 + kGp1dLongTierSBytes);
-
+// ---- the long-object tier of the per-band GP (gp1d_tiers.hpp)
 // slabs: kGp1dLongTierGrid Gram matrices, then kGp1dLongTierGrid working sets.  Light curves of more than kLongCap rows keep
 // the NaN row and status -100 the tier-5 launch wrote.
 __global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B, Bins bins, double* out, int ld, int col0, int32_t* status,
@@ -1328,11 +1293,12 @@ int SetLaunch::launch_gp1d(double* kslab) const {
     for (int ti = last; ti >= 0; --ti) {
         const int nan_from = nan_from_of(ti, last);
         int rc = 0;
-        switch (ti) {
-            case 0: rc = gp1d_tier<64, 64, kGp1dThreads, 32, 3>(ti, nan_from); break;
-            case 1: rc = gp1d_tier<112, 112, kGp1dThreads, 32, 2>(ti, nan_from); break;
-            case 2: rc = gp1d_tier<160, 160, kGp1dThreads, 64, 1>(ti, nan_from); break;
-            default: rc = gp1d_tier<160, 768, kGp1dThreads, 64, 1>(ti, nan_from, kslab); break;
+        // the table of gp1d_tiers.hpp; tiers 3..5 share its last row, the only one with a global-scratch matrix
+        switch ((ti < kGp1dKernelTiers) ? ti : kGp1dKernelTiers - 1) {
+#define X(id, NP, ROWCAP, WNP, MW) \
+            case id: rc = gp1d_tier<NP, ROWCAP, kGp1dThreads, WNP, MW>(ti, nan_from, (ROWCAP > NP) ? kslab : nullptr); break;
+            LCFE_GP1D_KERNEL_TIERS(X)
+#undef X
         }
         if (rc) return rc;
         ++*n_launch;

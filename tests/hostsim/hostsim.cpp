@@ -118,6 +118,26 @@ extern "C" int hostsim_gp1d(int64_t n_obj, const int64_t* offsets, const double*
     return 0;
 }
 
+// the per-band objective alone (tests/test_gp1d_eval_cpu.py; the device counterpart is tests/devprobe/gp1d_probe.hip): m
+// prepared points -- what gp1d_band leaves in S.t, S.y, S.e2 -- and ne evaluations, evaluation e on the first n_e[e] points
+// at th_e[e][0..3).  f: [ne], g: [ne][3], alpha: [ne][m].  Returns 1 on sizes outside the working set.
+extern "C" int hostsim_gp1d_eval(int m, const double* t, const double* y, const double* e2, int ne, const int* n_e,
+                                 const double* th_e, double* f, double* g, double* alpha) {
+    using W = WaveHost;
+    constexpr int NP = 768;
+    if (m < 1 || m + 1 > NP || ne < 0) return 1;
+    for (int e = 0; e < ne; ++e)
+        if (n_e[e] < 1 || n_e[e] > m) return 1;
+    auto S = std::make_unique<Gp1dLds<NP, 1>>();
+    std::vector<double> K((size_t)gp_store_doubles(NP));
+    for (int i = 0; i < m; ++i) { S->t[i] = t[i]; S->y[i] = y[i]; S->e2[i] = e2[i]; }
+    for (int e = 0; e < ne; ++e) {
+        gp1d_eval<W, NP, double*>(th_e + 3 * e, n_e[e], *S, K.data(), f[e], g + 3 * e);
+        for (int i = 0; i < n_e[e]; ++i) alpha[(size_t)e * m + i] = S->alpha[i];
+    }
+    return 0;
+}
+
 // ---- bounded L-BFGS-B (csrc/lbfgsb_box.hpp) with the objective supplied by the caller: the test
 // drives it with the same Python function it hands to scipy.optimize.minimize.
 #include "../../mallorn-astrophysics_amd/csrc/lbfgsb_box.hpp"
