@@ -318,6 +318,12 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
         // for the next step.  Tile rows are handed out by a ticket (longest first), so wavefront 0 simply takes fewer rows.
         // Operation for operation the arithmetic of the step-by-step schedule: bit-identical results.
         constexpr bool kLookAhead = LDS::kLookAhead;
+        // Row-update loops over a compacted trip list (only the tiles a pass stores; below) where that was measured to win
+        // (DESIGN section 7): the 64- and 160-row tiers (one tile per pass, matrix in LDS) and the 512-row tier (fused, 256
+        // registers).  The fused 112- and 240-row tiers (128 registers, bound by the fabric) did not move beyond their spread
+        // and their scratch frame grew, so they keep the loop over all columns with masked stores; so do the 768-row tier,
+        // the long tier and the per-band GP, which the benchmark does not time.
+        constexpr bool kCompactTrips = LDS::kLookAhead && LDS::kInLds && (LDS::kFuse ? NP > 240 : NP <= 160);
         double pn1[4] = {0, 0, 0, 0};         // wavefront 0: -(-D^-1) of the next pivot block, Gauss-Jordan layout
         // (the second inverse of a fused pass waits in the staging tile, which is idle from the end of one look-ahead to the
         //  start of the next: the lane that wrote an element is the one that reads it back)
@@ -566,6 +572,48 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
                         const double n1[4] = {-w1[0], -w1[1], -w1[2], -w1[3]};
                         constexpr int UNR = 2;      // tiles in flight (four were measured slower, also at 256 registers per lane; so was
                                                     // requesting the next trip's tiles ahead of this trip's products: +8 %, 11 more spilled registers)
+                        if constexpr (kCompactTrips) {
+                        // The row's trip list holds the tiles this pass stores and no others: columns 0 .. i without the pivot
+                        // column b (the row's owner has written W2_i there, above) and without wavefront 0's look-ahead tiles,
+                        // which end the rows a2 and b2.  Entry q of the list is column q + (q >= b); all of it wave-uniform.
+                        // (tests/gp_sweep_tiles.py restates this index arithmetic: change both together)
+                        const int cnt = i + 1 - ((i > b) ? 1 : 0) - ((la1 && i == a2) ? 1 : 0) - ((la2 && i == b2) ? 2 : 0);
+                        // K tiles in flight from entry q0 on; the row's last trip takes the one tile that is left, not a
+                        // second copy of it
+                        auto trip = [&](auto k_tag, int q0) {
+                            constexpr int K = decltype(k_tag)::value;
+                            gp_v4f64 c[K];
+                            double b1[K][4], b2v[K][4];
+                            int jc[K];
+#pragma unroll
+                            for (int u = 0; u < K; ++u) {
+                                const int q = q0 + u, j = q + ((q >= b) ? 1 : 0);
+                                jc[u] = j;
+                                // pivot column of step a: the tile becomes W1_i itself, its old content is not read
+                                if (j != a) c[u] = load_tile(A + tile_base(i, j));
+#pragma unroll
+                                for (int kc = 0; kc < 4; ++kc) { b1[u][kc] = S.V[4 * kc + lr][(j << 4) + lc]; b2v[u][kc] = V2[4 * kc + lr][(j << 4) + lc]; }
+                            }
+#pragma unroll
+                            for (int u = 0; u < K; ++u) {
+                                if (jc[u] == a) c[u] = w_dlayout(dA1, S.V, i);
+                                else {
+#pragma unroll
+                                    for (int kc = 0; kc < 4; ++kc) c[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(n1[kc], b1[u][kc], c[u], 0, 0, 0);
+                                }
+                            }
+#pragma unroll
+                            for (int kc = 0; kc < 4; ++kc)
+#pragma unroll
+                                for (int u = 0; u < K; ++u) c[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(n2[kc], b2v[u][kc], c[u], 0, 0, 0);
+#pragma unroll
+                            for (int u = 0; u < K; ++u) store_tile(A + tile_base(i, jc[u]), c[u]);
+                        };
+                        int q0 = 0;
+                        for (; q0 + UNR <= cnt; q0 += UNR) trip(std::integral_constant<int, UNR>{}, q0);
+                        if (q0 < cnt) trip(std::integral_constant<int, 1>{}, q0);
+                        } else {
+                        // the 112- and 240-row tiers: trips over columns 0 .. i as they are, masked stores (see kCompactTrips)
                         for (int j0 = 0; j0 <= i; j0 += UNR) {
                             gp_v4f64 c[UNR];
                             double b1[UNR][4], b2v[UNR][4];
@@ -604,6 +652,7 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
 #pragma unroll
                                 for (int v = 0; v < 4; ++v) T[((lr + 4 * v) << 4) + lc] = c[u][v];
                             }
+                        }
                         }
                     }
                     W::sync();
@@ -674,6 +723,54 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
                 }
                 const double na[4] = {-wt[0], -wt[1], -wt[2], -wt[3]};
                 constexpr int UNR = 4;                                     // tiles in flight (independent accumulators)
+                if constexpr (kCompactTrips) {
+                // (tests/gp_sweep_tiles.py restates this index arithmetic: change both together)
+                // The row's trip list holds the tiles this step stores and no others: columns 0 .. i, below the pivot row
+                // without the pivot column kt (W_i has been written there, above) and, in row kt + 1, without wavefront 0's
+                // look-ahead tile, which ends that row.  Entry q of the list is column q + (q >= jskip); all of it wave-uniform.
+                const int jskip = (i > kt) ? kt : nt;
+                const int cnt = i + 1 - ((i > kt) ? 1 : 0) - ((la && i == kt + 1) ? 1 : 0);
+                // K tiles in flight from entry q0 on; the row's last trip takes the tiles that are left, not copies of the last
+                auto trip = [&](auto k_tag, int q0) {
+                    constexpr int K = decltype(k_tag)::value;
+                    gp_v4f64 c[K];
+                    double bv[K][4];
+                    int jc[K];
+#pragma unroll
+                    for (int u = 0; u < K; ++u) {
+                        const int q = q0 + u, j = q + ((q >= jskip) ? 1 : 0);
+                        jc[u] = j;
+                        c[u] = load_tile(A + tile_base(i, j));
+#pragma unroll
+                        for (int kc = 0; kc < 4; ++kc) bv[u][kc] = S.V[4 * kc + lr][(j << 4) + lc];
+                    }
+#pragma unroll
+                    for (int kc = 0; kc < 4; ++kc)
+#pragma unroll
+                        for (int u = 0; u < K; ++u) c[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(na[kc], bv[u][kc], c[u], 0, 0, 0);
+#pragma unroll
+                    for (int u = 0; u < K; ++u) {
+                        const int j = jc[u];
+                        KP T = A + tile_base(i, j);
+                        if (i != kt) store_tile(T, c[u]);
+                        else {
+                            // partial pivot tile row: only its non-pivot rows (and, in the diagonal tile, columns) move
+#pragma unroll
+                            for (int v = 0; v < 4; ++v)
+                                if (lr + 4 * v >= bs && (j != kt || lc >= bs)) T[((lr + 4 * v) << 4) + lc] = c[u][v];
+                        }
+                    }
+                };
+                int q0 = 0;
+                for (; q0 + UNR <= cnt; q0 += UNR) trip(std::integral_constant<int, UNR>{}, q0);
+                switch (cnt - q0) {
+                    case 3: trip(std::integral_constant<int, 3>{}, q0); break;
+                    case 2: trip(std::integral_constant<int, 2>{}, q0); break;
+                    case 1: trip(std::integral_constant<int, 1>{}, q0); break;
+                    default: break;
+                }
+                } else {
+                // the 768-row tier, the long tier and the per-band GP: trips over columns 0 .. i as they are, masked stores
                 for (int j0 = 0; j0 <= i; j0 += UNR) {
                     gp_v4f64 c[UNR];
                     double bv[UNR][4];
@@ -708,6 +805,7 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
                                 if (lr + 4 * v >= bs && (j != kt || lc >= bs)) T[((lr + 4 * v) << 4) + lc] = c[u][v];
                         }
                     }
+                }
                 }
             }
             W::sync();
