@@ -13,6 +13,7 @@
 #include "fits.hpp"      // wave_median
 #include "lbfgsb.hpp"
 #include "stage.hpp"
+#include "gp_tier_table.hpp"     // gp_store_doubles
 
 namespace lcfe {
 
@@ -26,7 +27,6 @@ constexpr double GP_LOG_2PI = 1.8378770664093453;
 // 512-byte LDS accesses, and a tile is one coalesced 2 KiB piece of global scratch.
 LCFE_HD int tile_base(int ti, int tj) { return (ti * (ti + 1) / 2 + tj) * 256; }            // tj <= ti
 LCFE_HD int tri_index(int i, int j) { return tile_base(i >> 4, j >> 4) + ((i & 15) << 4) + (j & 15); }   // j <= i
-LCFE_HD constexpr int gp_store_doubles(int np) { return ((np + 15) / 16) * ((np + 15) / 16 + 1) / 2 * 256; }
 
 #if defined(__HIPCC__)
 typedef __attribute__((address_space(3))) double lds_double;     // LDS-qualified element type: keeps ds_* addressing across calls
@@ -85,11 +85,15 @@ template <int NP, int LDV> struct GpSmallArrays<NP, LDV, true> {
 template <bool ON> struct GpStageTile { double stage[1]; };
 template <> struct GpStageTile<true> { double stage[GP_B * GP_B]; };
 
-template <int NP, int NW = 4, bool FUSE = false, bool LOOKAHEAD = true, bool IN_LDS = true>
+template <int NP, int NW = 4, bool FUSE = false, bool LOOKAHEAD = true, bool IN_LDS = true, bool COMPACT = false>
 struct GpLds {
     static constexpr bool kFuse = FUSE;
     static constexpr bool kLookAhead = LOOKAHEAD && NW >= 4;
     static constexpr bool kInLds = IN_LDS;    // false: the long-object tier keeps this working set in global scratch
+    // row-update loops of the sweep over compacted trip lists (gp_sweep_inverse): per tier, from the COMPACT column of
+    // gp_tier_table.hpp; the per-band GP, the long-object tier and the host simulation do not set it
+    static constexpr bool kCompactTrips = COMPACT;
+    static_assert(!COMPACT || (kLookAhead && IN_LDS), "compacted trip lists: only with the pivot look-ahead and an LDS working set");
     double t[NP], y[NP], e2[NP];              // valid points: time (from first valid), flux/scale, (err/scale)^2
     double alpha[NP];                         // K^-1 r
     GpSmallArrays<NP, gp_panel_ld(NP), FUSE> sm;
@@ -319,11 +323,12 @@ LCFE_FN bool gp_sweep_inverse(KP A, int n, LDS& S, double& logdet) {
         // Operation for operation the arithmetic of the step-by-step schedule: bit-identical results.
         constexpr bool kLookAhead = LDS::kLookAhead;
         // Row-update loops over a compacted trip list (only the tiles a pass stores; below) where that was measured to win
-        // (DESIGN section 7): the 64- and 160-row tiers (one tile per pass, matrix in LDS) and the 512-row tier (fused, 256
-        // registers).  The fused 112- and 240-row tiers (128 registers, bound by the fabric) did not move beyond their spread
-        // and their scratch frame grew, so they keep the loop over all columns with masked stores; so do the 768-row tier,
-        // the long tier and the per-band GP, which the benchmark does not time.
-        constexpr bool kCompactTrips = LDS::kLookAhead && LDS::kInLds && (LDS::kFuse ? NP > 240 : NP <= 160);
+        // (DESIGN section 7): a flag of the working set, set per tier by the COMPACT column of gp_tier_table.hpp -- the 64-
+        // and 160-row tiers (one tile per pass, matrix in LDS) and the 512-row tier (fused, 256 registers).  The fused 112-
+        // and 240-row tiers (128 registers, bound by the fabric) did not move beyond their spread and their scratch frame
+        // grew, so they keep the loop over all columns with masked stores; so do the 768-row tier, the long tier and the
+        // per-band GP, which the benchmark does not time.
+        constexpr bool kCompactTrips = LDS::kCompactTrips;
         double pn1[4] = {0, 0, 0, 0};         // wavefront 0: -(-D^-1) of the next pivot block, Gauss-Jordan layout
         // (the second inverse of a fused pass waits in the staging tile, which is idle from the end of one look-ahead to the
         //  start of the next: the lane that wrote an element is the one that reads it back)

@@ -150,11 +150,7 @@ struct SetLaunch {
 __device__ __forceinline__ int set_bin_of(int64_t n) {
     return (n <= 128) ? 0 : (n <= 256) ? 1 : (n <= 512) ? 2 : (n <= 1024) ? 3 : (n <= 2048) ? 4 : 6;
 }
-// GP window on the ROW count of the object (>= its valid points); one row of the tile storage is the
-// augmented residual row, so the caps are NP - 1.
-__device__ __forceinline__ int gp_bin_of(int64_t n) {
-    return (n <= 63) ? 0 : (n <= 111) ? 1 : (n <= 159) ? 2 : (n <= kGpSmallNP - 1) ? 3 : (n <= kGpMidNP - 1) ? 4 : (n <= kGpGlobalNP - 1) ? 5 : 6;
-}
+// (the GP sets bin by gp_bin_of of gp_tier_table.hpp: a window on the ROW count of the object, >= its valid points)
 
 // One block bins 1024 consecutive objects: ballots give the rank inside a wave, an LDS scan the
 // wave's offset inside the block, one atomicAdd per (block, bin) the block's slice of the list --
@@ -951,27 +947,14 @@ __global__ __launch_bounds__(64, (BCAP <= 64 ? 2 : 1)) void powerlaw_fit_kernel(
 // lower-triangle tiles in LDS (NP <= 160) or, for longer light curves, in a per-workgroup slab of
 // global scratch.  Objects come from the tier's index list through a ticket counter (one object per
 // ticket: an L-BFGS-B run is 10^5..10^7 cycles and heavy-tailed).
-constexpr int kGpGlobalGrid = 256;
-constexpr int kGpSmallGrid = 512;
-constexpr size_t kGpSmallBytes = (size_t)kGpSmallGrid * gp_store_doubles(kGpSmallNP) * 8;
-constexpr size_t kGpMidBytes = (size_t)kGpGlobalGrid * gp_store_doubles(kGpMidNP) * 8;
-constexpr size_t kGpGlobalBytes = (size_t)kGpGlobalGrid * gp_store_doubles(kGpGlobalNP) * 8;
-constexpr int kGp112Grid = 1024, kGp160Grid = 512;
-constexpr size_t kGp112Bytes = kGp112Global ? (size_t)kGp112Grid * gp_store_doubles(112) * 8 : 0;
-constexpr size_t kGp160Bytes = kGp160Global ? (size_t)kGp160Grid * gp_store_doubles(160) * 8 : 0;
-
-template <int NP> struct gp_grid_cap { static constexpr int G = (NP == 112) ? kGp112Grid : ((NP == 160) ? kGp160Grid : ((NP == kGpSmallNP) ? kGpSmallGrid : kGpGlobalGrid)); };
-constexpr int kGpLongGrid = 8;
-constexpr size_t kGpLongSBytes = (sizeof(gp_working_set<kGpLongNP>::type) + 255) & ~(size_t)255;
-constexpr size_t kGpLongBytes = (size_t)kGpLongGrid * ((size_t)gp_store_doubles(kGpLongNP) * 8 + kGpLongSBytes);
-
 template <int NP, bool GLOBAL_K>
-__global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP, GLOBAL_K>::N)) void gp_kernel(BatchView B, Bins bins, int bin, int nan_from, double* out, int ld,
+__global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP>::N)) void gp_kernel(BatchView B, Bins bins, int bin, int nan_from, double* out, int ld,
                                                  int col0, int32_t* status, int st_ld, int st0, double* kscratch,
                                                  unsigned long long* ticket) {
-    using W = BlockDev<gp_threads<NP>::T>;
-    __shared__ GpLds<NP, W::NWAVES, gp_fuse<NP, GLOBAL_K>::F> S;
-    __shared__ double Klds[GLOBAL_K ? 1 : gp_store_doubles(NP)];
+    using Tier = GpTier<NP, GLOBAL_K>;
+    using W = typename Tier::W;
+    __shared__ typename Tier::Set S;
+    __shared__ double Klds[Tier::kLdsDoubles];
     __shared__ long long next_ticket;
     double* Kg = kscratch + (size_t)blockIdx.x * (size_t)gp_store_doubles(NP);
     const int count = bins.count(gp_list(bin));
@@ -983,29 +966,24 @@ __global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP, GLOBAL_K>::N)) voi
         double* row = out + i * (int64_t)ld + col0;
         int32_t* st = status ? status + i * (int64_t)st_ld + st0 : nullptr;
         ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n64, qnan()};
-        if constexpr (GLOBAL_K) {
-            gp_object<W, NP>(in, S, [&](const double* x, int n, double& f, double* g, bool need) {
-                gp_eval<W, NP, global_double*>(x, n, S, (global_double*)Kg, f, g, need); }, st);
-        } else {
-            gp_object<W, NP>(in, S, [&](const double* x, int n, double& f, double* g, bool need) {
-                gp_eval<W, NP, lds_double*>(x, n, S, (lds_double*)Klds, f, g, need); }, st);
-        }
+        gp_object<W, NP>(in, S, [&](const double* x, int n, double& f, double* g, bool need) {
+            Tier::eval(S, Tier::matrix(Klds, Kg), x, n, f, g, need); }, st);
         store_row<W>(S.out, row, GP_NCOL);
         __syncthreads();
     }
     nan_fill_bins<W>(bins, 1, nan_from, out, ld, col0, GP_NCOL, status, st_ld, st0, 4);
 }
 
-// the same loop for the long-object tier (slabs: kGpLongGrid Gram matrices, then kGpLongGrid working sets)
-__global__ __launch_bounds__(gp_threads<kGpLongNP>::T, 1) void gp_long_kernel(BatchView B, Bins bins, int bin, double* out, int ld, int col0,
-                                                                             int32_t* status, int st_ld, int st0, char* slabs,
-                                                                             unsigned long long* ticket) {
+// the same loop for the long-object tier (slabs: GpLongTier::kBytes)
+__global__ __launch_bounds__(kGpLongThreads, 1) void gp_long_kernel(BatchView B, Bins bins, int bin, double* out, int ld, int col0,
+                                                                   int32_t* status, int st_ld, int st0, char* slabs,
+                                                                   unsigned long long* ticket) {
+    using Tier = GpLongTier;
+    using W = Tier::W;
     constexpr int NP = kGpLongNP;
-    using W = BlockDev<gp_threads<NP>::T>;
-    using SL = gp_working_set<NP>::type;
     __shared__ long long next_ticket;
     double* Kg = reinterpret_cast<double*>(slabs) + (size_t)blockIdx.x * (size_t)gp_store_doubles(NP);
-    SL& S = *reinterpret_cast<SL*>(slabs + (size_t)kGpLongGrid * gp_store_doubles(NP) * 8 + (size_t)blockIdx.x * kGpLongSBytes);
+    Tier::Set& S = *reinterpret_cast<Tier::Set*>(slabs + (size_t)kGpLongGrid * gp_store_doubles(NP) * 8 + (size_t)blockIdx.x * Tier::kSetBytes);
     const int count = bins.count(gp_list(bin));
     const int* list = bins.list(gp_list(bin));
     for (;;) {
@@ -1014,8 +992,7 @@ __global__ __launch_bounds__(gp_threads<kGpLongNP>::T, 1) void gp_long_kernel(Ba
         const auto [i, s, n64] = take_object(B, list, pos);
         int32_t* st = status ? status + i * (int64_t)st_ld + st0 : nullptr;
         ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n64, qnan()};
-        gp_object<W, NP>(in, S, [&](const double* x, int n, double& f, double* g, bool need) {
-            gp_eval<W, NP, global_double*>(x, n, S, (global_double*)Kg, f, g, need); }, st);
+        gp_object<W, NP>(in, S, [&](const double* x, int n, double& f, double* g, bool need) { Tier::eval(S, Kg, x, n, f, g, need); }, st);
         store_row<W>(S.out, out + i * (int64_t)ld + col0, GP_NCOL);
         __syncthreads();
     }
@@ -1029,7 +1006,7 @@ __global__ __launch_bounds__(gp_threads<kGpLongNP>::T, 1) void gp_long_kernel(Ba
 constexpr int kGpSortThreads = 1024;
 __global__ __launch_bounds__(kGpSortThreads) void gp_sort_kernel(const int64_t* offsets, Bins bins) {
     const int tier = blockIdx.x;
-    const int hi = (tier == 0) ? 63 : (tier == 1) ? 111 : (tier == 2) ? 159 : (tier == 3) ? kGpSmallNP - 1 : (tier == 4) ? kGpMidNP - 1 : kGpGlobalNP - 1;
+    const int hi = gp_cap_of(tier);
     const int count = bins.count(gp_list(tier));
     const int* src = bins.list(gp_list(tier));
     int* dst = bins.list(gp_sorted_list(tier));
@@ -1066,11 +1043,10 @@ __global__ __launch_bounds__(kGpSortThreads) void gp_sort_kernel(const int64_t* 
     }
 }
 
-static_assert(kGpCaps[3] == kGpSmallNP - 1 && kGpCaps[4] == kGpMidNP - 1 && kGpCaps[5] == kGpGlobalNP - 1, "gp_bin_of and workspace.hpp");
-
 template <int NP, bool GLOBAL_K>
 int SetLaunch::gp_tier(int ti, int nan_from, hipStream_t q, double* kscratch, int64_t cap) const {
-    if (GLOBAL_K && (cap < 1 || cap > gp_grid_cap<NP>::G)) cap = gp_grid_cap<NP>::G;     // one slab of global scratch per workgroup
+    constexpr int kSlabs = gp_tier_row(NP).slabs;
+    if (GLOBAL_K && (cap < 1 || cap > kSlabs)) cap = kSlabs;     // one slab of global scratch per workgroup
     {
         // tuning knob: LCFE_GP_GRID_<rows>=k caps the workgroups of a tier (fewer Gram matrices in flight = more of them in L2)
         char name[40];
@@ -1082,7 +1058,7 @@ int SetLaunch::gp_tier(int ti, int nan_from, hipStream_t q, double* kscratch, in
                        st_ld, st0, kscratch, tickets + SET_GP2D * 8 + ti);
 }
 
-// kslab: the Gram-matrix slabs of the tiers in global scratch, in workspace order (WS_GP_SMALL .. WS_GP_160)
+// kslab[tier]: the tier's Gram-matrix slabs (WS_GP_TIER + tier; no bytes behind the pointer of a tier whose matrix is in LDS)
 int SetLaunch::launch_gp(const hipStream_t* gs, int ngs, double* const* kslab) const {
     hipStream_t stream2 = gs[(ngs > 1) ? 1 : 0];
     // (A variant that keeps the matrix in the REGISTERS of the workgroup -- 2-D block-cyclic tiles,
@@ -1134,18 +1110,15 @@ int SetLaunch::launch_gp(const hipStream_t* gs, int ngs, double* const* kslab) c
         hipStream_t q = gs[plan[pi].stream];
         int rc = 0;
         switch (ti) {
-            case 0: rc = gp_tier<64, false>(ti, nan_from, q, nullptr, cap); break;
-            case 1: rc = gp_tier<112, kGp112Global>(ti, nan_from, q, kslab[3], cap); break;
-            case 2: rc = gp_tier<160, kGp160Global>(ti, nan_from, q, kslab[4], cap); break;
-            case 3: rc = gp_tier<kGpSmallNP, true>(ti, nan_from, q, kslab[0], cap); break;
-            case 4: rc = gp_tier<kGpMidNP, true>(ti, nan_from, q, kslab[1], cap); break;
-            case 5: rc = gp_tier<kGpGlobalNP, true>(ti, nan_from, q, kslab[2], cap); break;
+#define X(id, NP, GK, ...) case id: rc = gp_tier<NP, GK>(ti, nan_from, q, kslab[id], cap); break;
+            LCFE_GP_TIERS(X)
+#undef X
         }
         if (rc) return rc;
         ++*n_launch;
-        // light curves of more than 767 rows (bin 6; NaN rows and status -100 from the launch above until this one has run)
-        if (ti == last && last == 5 && long_slabs) {
-            hipLaunchKernelGGL(gp_long_kernel, dim3(kGpLongGrid), dim3(gp_threads<kGpLongNP>::T), 0, q, B, bins, 6, out, ld, col0, status,
+        // light curves beyond the last tier's cap (bin 6; NaN rows and status -100 from the launch above until this one has run)
+        if (ti == last && last == kGpNumTiers - 1 && long_slabs) {
+            hipLaunchKernelGGL(gp_long_kernel, dim3(kGpLongGrid), dim3(kGpLongThreads), 0, q, B, bins, kGpNumTiers, out, ld, col0, status,
                                st_ld, st0, long_slabs, tickets + SET_GP2D * 8 + 7);
             HIP_TRY(hipGetLastError());
             ++*n_launch;
@@ -1592,14 +1565,14 @@ struct HostPathPool {
 HostPathPool g_pool[16];
 
 // what workspace.hpp takes from the kernels' own structures; every size a multiple of the regions' 256-byte rounding
-static_assert(kGpSmallBytes % 256 == 0 && kGpMidBytes % 256 == 0 && kGpGlobalBytes % 256 == 0 && kGp112Bytes % 256 == 0 && kGp160Bytes % 256 == 0 &&
-              kGp1dLongBytes % 256 == 0 && kGpLongBytes % 256 == 0 && kGp1dLongTierBytes % 256 == 0, "slab sizes");
-static_assert(SetTraits<SET_GP2D>::long_above == kGpGlobalNP - 1 && SetTraits<SET_GP1D>::long_above == kGpGlobalNP - 1, "last GP tier");
+// (the 2-D GP tiers' slabs: gp_tier_slab_bytes of gp_tier_table.hpp, which holds them to the same rounding)
+static_assert(kGp1dLongBytes % 256 == 0 && GpLongTier::kBytes % 256 == 0 && kGp1dLongTierBytes % 256 == 0, "slab sizes");
 const WsSizes kWsSizes = [] {
-    WsSizes z{{kGpSmallBytes, kGpMidBytes, kGpGlobalBytes, kGp112Bytes, kGp160Bytes}, kGp1dLongBytes, {}};
+    WsSizes z{{}, kGp1dLongBytes, {}};
+    for (int ti = 0; ti < kGpNumTiers; ++ti) z.gp_slab[ti] = gp_tier_slab_bytes(ti);
     for (int s = 0; s < NUM_ALL_SETS; ++s)
         z.long_slab[s] = for_set(s, [](auto tag) -> size_t {
-            if constexpr (tag() == SET_GP2D) return kGpLongBytes;
+            if constexpr (tag() == SET_GP2D) return GpLongTier::kBytes;
             else if constexpr (tag() == SET_GP1D) return kGp1dLongTierBytes;
             else return kLongGrid * long_slab_bytes<tag()>();
         });
@@ -1893,8 +1866,8 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
     unsigned long long* tickets = (unsigned long long*)d_workspace;
     int* counts = (int*)((char*)d_workspace + kWsCounts);
     int* lists = (int*)L.at(d_workspace, WS_LISTS);
-    double* gp_slab[5];
-    for (int k = 0; k < 5; ++k) gp_slab[k] = (double*)L.at(d_workspace, WS_GP_SMALL + k);
+    double* gp_slab[kGpNumTiers];
+    for (int k = 0; k < kGpNumTiers; ++k) gp_slab[k] = (double*)L.at(d_workspace, WS_GP_TIER + k);
     // the slabs of the long-object tier, when the workspace was sized with lcfe_workspace_bytes_for(.., max_len)
     char* long_slab[NUM_ALL_SETS] = {};
     if (workspace_bytes >= L.total)

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "feature_sets.hpp"
+#include "gp_tier_table.hpp"
 
 namespace lcfe {
 
@@ -30,6 +31,8 @@ constexpr int tier_list(int group, int bin) { return group * kNumBins + bin; }
 constexpr int gp_list(int tier) { return tier_list(1, tier); }
 constexpr int gp_sorted_list(int tier) { return kGpSortedList + tier; }
 constexpr int kGpLongList = gp_list(kNumBins - 1);    // light curves beyond the largest Gram-matrix tier
+static_assert(kGpNumTiers + 1 == kNumBins, "one bin per tier of gp_tier_table.hpp + the long light curves (gp_bin_of)");
+static_assert(SetTraits<SET_GP2D>::long_above == kGpLastCap && SetTraits<SET_GP1D>::long_above == kGpLastCap, "last GP tier");
 
 // ---- header: [0, 1024) ticket counters (8 per set up to the extension set, then the fit lists'), [1024, 2048) counts (the
 // lists' lengths, then the fit lists'), [2048, 2304) ticket counters of the registered sets (8 per set)
@@ -63,7 +66,7 @@ constexpr int kPlFitsB = 6;            // ... the exponential and the linear mod
 // ---- regions, in workspace order
 enum WsRegion {
     WS_HEADER, WS_LISTS,
-    WS_GP_SMALL, WS_GP_MID, WS_GP_GLOBAL, WS_GP_112, WS_GP_160,                 // Gram-matrix slabs of the 2-D GP tiers
+    WS_GP_TIER, WS_GP_TIER_LAST = WS_GP_TIER + kGpNumTiers - 1,                 // + tier: Gram-matrix slabs of the 2-D GP tier
     WS_BAZIN_ROWS, WS_BAZIN_PBOFF, WS_BAZIN_FITS,                               // pt / pf / pe, pboff, fits
     WS_PL_ROWS, WS_PL_PEAK, WS_PL_PBOFF, WS_PL_KK, WS_PL_FITS_A, WS_PL_FITS_B,  // tp / fp, peak / sstot, pboff, kk, fitsA, fitsB
     WS_GP1D,                                                                    // per-band GP: slabs of the long bands
@@ -73,7 +76,7 @@ enum WsRegion {
 
 // the sizes that come from the kernels' own structures (lcfe.hip fills them in)
 struct WsSizes {
-    size_t gp_slab[5];                 // WS_GP_SMALL .. WS_GP_160
+    size_t gp_slab[kGpNumTiers];       // by tier: gp_tier_slab_bytes (no bytes for a tier whose matrix is in LDS)
     size_t gp1d_slab;
     size_t long_slab[NUM_ALL_SETS];    // all slabs of the set's long-object tier (0: bit is no set)
 };
@@ -92,7 +95,7 @@ struct WsLayout {
         const bool gp2d = mask & (1 << SET_GP2D), bazin = mask & (1 << SET_BAZIN), pl = mask & (1 << SET_POWERLAW);
         take(WS_HEADER, kWsHeader);
         take(WS_LISTS, (size_t)(n_obj > 0 ? n_obj : 0) * kNumLists * sizeof(int));
-        for (int k = 0; k < 5; ++k) take(WS_GP_SMALL + k, gp2d ? z.gp_slab[k] : 0);
+        for (int k = 0; k < kGpNumTiers; ++k) take(WS_GP_TIER + k, gp2d ? z.gp_slab[k] : 0);
         take(WS_BAZIN_ROWS, bazin ? 3 * sizeof(double) * np : 0);
         take(WS_BAZIN_PBOFF, bazin ? kBandOffsets * sizeof(int) * no : 0);
         take(WS_BAZIN_FITS, bazin ? sizeof(int) * kFitTiers * kBazinFits * no : 0);
@@ -128,13 +131,7 @@ inline int last_tier(int64_t max_len, int max_tier) {
     return last;
 }
 inline int nan_from_of(int ti, int last) { return (ti == last) ? ti + 1 : kNumBins; }
-// the GP sets bin by the rows of the light curve against the Gram-matrix tiers (one row is the augmented residual row)
-constexpr int kGpCaps[6] = {63, 111, 159, 239, 511, 767};
-inline int gp_last_tier(int64_t max_len) {
-    int last = 0;
-    while (last < 5 && kGpCaps[last] < max_len) ++last;
-    return last;
-}
+// (the GP sets bin by the rows of the light curve against the Gram-matrix tiers: gp_last_tier of gp_tier_table.hpp)
 
 // ---- workgroups of a persistent launch: as many as the chip holds at once (the occupancy query may say 0: at least one
 // per CU), at most `cap` (0: no cap), and no more than there are tickets of `per_ticket` work items.  0: nothing to launch.

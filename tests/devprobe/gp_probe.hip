@@ -22,7 +22,7 @@ namespace {
 
 constexpr int kGpMaxEvals = 16;            // evaluations of one call
 constexpr int kScratchOverrun = -3;        // the guard region behind the Gram slab was written
-constexpr int kGpTiers = 7;
+constexpr int kGpTiers = kGpNumTiers + 1;   // + the long-object tier
 
 struct GpProbeArgs {
     const double *t, *y, *e2;              // m prepared points: what gp_object leaves in S.t, S.y, S.e2
@@ -61,46 +61,35 @@ __device__ __forceinline__ void gp_probe_run(const GpProbeArgs& a, LDS& S, Ev&& 
     }
 }
 
-// the LDS and global-scratch tiers: the declarations of gp_kernel<NP, GLOBAL_K>
+// the LDS and global-scratch tiers: a tier of the table, as gp_kernel<NP, GLOBAL_K> declares it
 template <int NP, bool GLOBAL_K>
-__global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP, GLOBAL_K>::N)) void k_gp_eval(GpProbeArgs a, double* kscratch) {
-    using W = BlockDev<gp_threads<NP>::T>;
-    __shared__ GpLds<NP, W::NWAVES, gp_fuse<NP, GLOBAL_K>::F> S;
-    __shared__ double Klds[GLOBAL_K ? 1 : gp_store_doubles(NP)];
-    double* Kg = kscratch;
-    if constexpr (GLOBAL_K) {
-        gp_probe_run<W>(a, S, [&](const double* x, int n, double& f, double* g, bool need) {
-            gp_eval<W, NP, global_double*>(x, n, S, (global_double*)Kg, f, g, need); });
-    } else {
-        gp_probe_run<W>(a, S, [&](const double* x, int n, double& f, double* g, bool need) {
-            gp_eval<W, NP, lds_double*>(x, n, S, (lds_double*)Klds, f, g, need); });
-    }
+__global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP>::N)) void k_gp_eval(GpProbeArgs a, double* kscratch) {
+    using Tier = GpTier<NP, GLOBAL_K>;
+    __shared__ typename Tier::Set S;
+    __shared__ double Klds[Tier::kLdsDoubles];
+    gp_probe_run<typename Tier::W>(a, S, [&](const double* x, int n, double& f, double* g, bool need) {
+        Tier::eval(S, Tier::matrix(Klds, kscratch), x, n, f, g, need); });
 }
 
-// the long-object tier: the declarations of gp_long_kernel (working set in global memory)
-__global__ __launch_bounds__(gp_threads<kGpLongNP>::T, 1) void k_gp_eval_long(GpProbeArgs a, double* kscratch, char* wset) {
-    constexpr int NP = kGpLongNP;
-    using W = BlockDev<gp_threads<NP>::T>;
-    using SL = gp_working_set<NP>::type;
-    double* Kg = kscratch;
-    SL& S = *reinterpret_cast<SL*>(wset);
-    gp_probe_run<W>(a, S, [&](const double* x, int n, double& f, double* g, bool need) {
-        gp_eval<W, NP, global_double*>(x, n, S, (global_double*)Kg, f, g, need); });
+// the long-object tier, as gp_long_kernel declares it (working set in global memory)
+__global__ __launch_bounds__(kGpLongThreads, 1) void k_gp_eval_long(GpProbeArgs a, double* kscratch, char* wset) {
+    using Tier = GpLongTier;
+    Tier::Set& S = *reinterpret_cast<Tier::Set*>(wset);
+    gp_probe_run<Tier::W>(a, S, [&](const double* x, int n, double& f, double* g, bool need) { Tier::eval(S, kscratch, x, n, f, g, need); });
 }
 
-// tier ids of the ABI, in the order of gp_bin_of: {NP, matrix in global scratch}
-#define GP_PROBE_TIERS(X) \
-    X(0, 64, false) X(1, 112, kGp112Global) X(2, 160, kGp160Global) X(3, kGpSmallNP, true) X(4, kGpMidNP, true) X(5, kGpGlobalNP, true)
-
-struct TierInfo { int np, threads, global_k, fuse, long_tier; };
+// tier ids of the ABI: the ids of LCFE_GP_TIERS, then the long-object tier
+struct TierInfo { int np, threads, global_k, fuse, long_tier, compact; };
 bool tier_info(int tier, TierInfo& o) {
+    if (tier == kGpTiers - 1) { o = {kGpLongNP, kGpLongThreads, 1, 0, 1, GpLongTier::Set::kCompactTrips}; return true; }
+    if (tier < 0 || tier >= kGpNumTiers) return false;
+    // what the tier's kernel is built with, not the row it was built from
     switch (tier) {
-#define X(id, NP, GK) case id: o = {NP, gp_threads<NP>::T, GK ? 1 : 0, gp_fuse<NP, GK>::F ? 1 : 0, 0}; return true;
-        GP_PROBE_TIERS(X)
+#define X(id, NP, GK, ...) case id: { using S = GpTier<NP, GK>::Set; o = {NP, GpTier<NP, GK>::W::LANES, GK, S::kFuse, 0, S::kCompactTrips}; } break;
+        LCFE_GP_TIERS(X)
 #undef X
-        case kGpTiers - 1: o = {kGpLongNP, gp_threads<kGpLongNP>::T, 1, 0, 1}; return true;
     }
-    return false;
+    return true;
 }
 
 }  // namespace
@@ -110,11 +99,12 @@ extern "C" {
 int devprobe_gp_tiers() { return kGpTiers; }
 int devprobe_gp_max_evals() { return kGpMaxEvals; }
 
-// o[5]: row capacity NP, threads of the workgroup, matrix in global scratch, fused sweep, working set in global memory
+// o[6]: row capacity NP, threads of the workgroup, matrix in global scratch, fused sweep, working set in global memory,
+// compacted trip lists
 int devprobe_gp_tier_info(int tier, int* o) {
     TierInfo ti;
     if (!tier_info(tier, ti)) return kBadShape;
-    o[0] = ti.np; o[1] = ti.threads; o[2] = ti.global_k; o[3] = ti.fuse; o[4] = ti.long_tier;
+    o[0] = ti.np; o[1] = ti.threads; o[2] = ti.global_k; o[3] = ti.fuse; o[4] = ti.long_tier; o[5] = ti.compact;
     return 0;
 }
 
@@ -155,16 +145,16 @@ int devprobe_gp_eval(int tier, int m, const double* t, const unsigned char* band
     if (ks) c.err = hipMemset(ks, kFill, kbytes + kPad);
     char* ws = nullptr;
     if (ti.long_tier) {
-        const size_t wbytes = (sizeof(gp_working_set<kGpLongNP>::type) + 255) & ~(size_t)255;
+        const size_t wbytes = GpLongTier::kSetBytes;
         ws = (char*)c.alloc(wbytes);
         if (ws && c.ok()) c.err = hipMemset(ws, kFill, wbytes);
     }
     if (c.ok()) {
         switch (tier) {
-#define X(id, NP, GK) case id: k_gp_eval<NP, GK><<<1, gp_threads<NP>::T>>>(a, (double*)ks); break;
-            GP_PROBE_TIERS(X)
+#define X(id, NP, GK, ...) case id: k_gp_eval<NP, GK><<<1, gp_threads<NP>::T>>>(a, (double*)ks); break;
+            LCFE_GP_TIERS(X)
 #undef X
-            default: k_gp_eval_long<<<1, gp_threads<kGpLongNP>::T>>>(a, (double*)ks, ws); break;
+            default: k_gp_eval_long<<<1, kGpLongThreads>>>(a, (double*)ks, ws); break;
         }
     }
     unsigned char guard[kPad];

@@ -2,8 +2,9 @@
 
 18 synthetic light curves, three per tier of `gp_kernel`: the first valid-point count the tier takes, the last one
 (n + 1 = NP, the augmented row in the last row of the last tile) and one that leaves a partial last tile next to the
-augmented row.  The counts follow from `gp_bin_of` / `kGpCaps` (63, 111, 159, 239, 511, 767) and the `n >= 10`,
-`n + 1 <= NP` rules of `gp_object`.  Every row of the generator is valid, so the row count is the valid-point count.
+augmented row.  The counts follow from the caps of csrc/gp_tier_table.hpp (63, 111, 159, 239, 511, 767; restated here and
+held against the table by tests/test_gp_tier_table_cpu.py) and the `n >= 10`, `n + 1 <= NP` rules of `gp_object`.  Every
+row of the generator is valid, so the row count is the valid-point count.
 """
 import numpy as np
 

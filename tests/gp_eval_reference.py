@@ -28,7 +28,8 @@ FIXTURE = "golden_gp_eval.npz"
 LONG_NP = 2048
 LONG_ROWS = 1100
 
-# per tier (row capacity NP, in the order of gp_bin_of): the three counts of the tier pin -- first, partial last tile,
+# per tier (row capacity NP, in the order of csrc/gp_tier_table.hpp; tests/test_gp_tier_table_cpu.py holds the keys, first
+# counts and caps against it): the three counts of the tier pin -- first, partial last tile,
 # last = NP - 1 -- then one with n % 16 == 0 (the augmented row opens a tile of its own) and one with n % 16 == 1.
 # Long-object tier: its first count and the counts around a full tile row.
 COUNTS = {64: (10, 47, 63, 48, 49), 112: (64, 95, 111, 96, 97), 160: (112, 143, 159, 144, 145),

@@ -29,14 +29,15 @@ column b (fused) or kt (single, rows below the pivot row), and the look-ahead ti
 list.  A trip takes UNR entries (2 fused, 4 single); the row's last trip takes what is left.
 
 This file restates the index arithmetic of gp_sweep_inverse's `kCompactTrips` branches (cnt, jskip, q + (q >= skip)) and
-the tier table of csrc/gp_tiers.hpp / gp_bin_of: a change there is made here too.  COMPACT names the tiers built with
-the compacted lists (gp.hpp: kCompactTrips); the others run `padded_row_trips` and store the same tiles.
+the tier table of csrc/gp_tier_table.hpp: a change there is made here too (tests/test_gp_tier_table_cpu.py holds TIERS and
+COMPACT against it).  COMPACT names the tiers built with the compacted lists (the table's COMPACT column, GpLds::
+kCompactTrips); the others run `padded_row_trips` and store the same tiles.
 """
 
 GP_B = 16
 UNR_FUSED, UNR_SINGLE = 2, 4
 LONG_NP = 2048
-# row capacity NP -> (smallest n the tier takes, its cap, fused sweep, pivot look-ahead): gp_bin_of, csrc/gp_tiers.hpp
+# row capacity NP -> (smallest n the tier takes, its cap, fused sweep, pivot look-ahead): csrc/gp_tier_table.hpp
 TIERS = {64: (10, 63, False, True), 112: (64, 111, True, True), 160: (112, 159, False, True),
          240: (160, 239, True, True), 512: (240, 511, True, True), 768: (512, 767, False, True),
          LONG_NP: (768, 2047, False, False)}

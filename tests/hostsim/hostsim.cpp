@@ -68,6 +68,19 @@ extern "C" int hostsim_gp_eval(int m, const double* t, const uint8_t* band, cons
     return 0;
 }
 
+// the tier table of the 2-D GP (csrc/gp_tier_table.hpp), for the tests' own restatements of it (tests/test_gp_tier_table_cpu.py)
+extern "C" int hostsim_gp_tiers() { return kGpNumTiers; }
+// o[8]: row capacity NP, first row count, cap, threads, matrix in global scratch, fused sweep, compacted trip lists, slabs
+extern "C" int hostsim_gp_tier_info(int ti, int* o) {
+    if (ti < 0 || ti >= kGpNumTiers) return 1;
+    const GpTierRow& r = kGpTierTable[ti];
+    const int v[8] = {r.np, gp_tier_first(ti), gp_tier_cap(ti), r.threads, r.global_k, r.fuse, r.compact, r.slabs};
+    // the binning agrees with the caps: a tier takes its first count and its cap, and nothing beyond
+    if (gp_bin_of(v[1]) != ti || gp_bin_of(v[2]) != ti || gp_bin_of(v[2] + 1) != ti + 1 || gp_cap_of(ti) != v[2]) return 2;
+    for (int k = 0; k < 8; ++k) o[k] = v[k];
+    return 0;
+}
+
 extern "C" int hostsim_extract(int set, int64_t n_obj, const int64_t* offsets, const double* t,
                                const double* flux, const double* err, const uint8_t* band,
                                const double* z, double* out, int32_t* status) {

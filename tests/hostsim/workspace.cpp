@@ -3,7 +3,8 @@
 //
 // The sizes that come from the kernels' structures (WsSizes) are STAND-INS here: the real ones are sizeof()s of the
 // device-side working sets in lcfe.hip, which a host build cannot reach.  The stand-ins are deliberately no multiples of
-// 256 bytes, so that the rounding of every region is exercised; the real sizes are pinned by test_workspace_cpu.py.
+// 256 bytes, so that the rounding of every region is exercised; the real sizes are pinned by test_workspace_cpu.py.  The
+// 2-D GP's slabs, one region per tier of csrc/gp_tier_table.hpp, are checked with the table's own sizes as well.
 #include <cstdio>
 #include <cstdlib>
 
@@ -22,7 +23,7 @@ static int g_failed = 0;
 static size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 
 static WsSizes stand_in_sizes() {
-    WsSizes z{{1000001, 2000003, 3000005, 400007, 0}, 500009, {}};
+    WsSizes z{{0, 400007, 0, 1000001, 2000003, 3000005}, 500009, {}};
     for (int s = 0; s < NUM_ALL_SETS; ++s) z.long_slab[s] = set_known(s) ? 100000 + 4099 * (size_t)s : 0;
     return z;
 }
@@ -41,7 +42,7 @@ static void check_layout(const WsSizes& z, int mask, int64_t no, int64_t np, int
     CHECK(T.off[WS_HEADER] == 0 && T.bytes[WS_HEADER] == 2304 && T.off[WS_LISTS] == 2304, "header");
     // a set that is not in the mask has no region; one that is has its regions
     const bool gp2d = mask & (1 << SET_GP2D), bazin = mask & (1 << SET_BAZIN), pl = mask & (1 << SET_POWERLAW), gp1d = mask & (1 << SET_GP1D);
-    for (int k = 0; k < 5; ++k) CHECK(T.bytes[WS_GP_SMALL + k] == (gp2d ? z.gp_slab[k] : 0), "mask %d GP slab %d", mask, k);
+    for (int k = 0; k < kGpNumTiers; ++k) CHECK(T.bytes[WS_GP_TIER + k] == (gp2d ? z.gp_slab[k] : 0), "mask %d GP slab of tier %d", mask, k);
     for (int r = WS_BAZIN_ROWS; r <= WS_BAZIN_FITS; ++r) CHECK((T.bytes[r] != 0) == bazin, "mask %d Bazin region %d", mask, r);
     for (int r = WS_PL_ROWS; r <= WS_PL_FITS_B; ++r) CHECK((T.bytes[r] != 0) == pl, "mask %d decline-fit region %d", mask, r);
     CHECK(T.bytes[WS_GP1D] == (gp1d ? z.gp1d_slab : 0), "mask %d per-band GP slab", mask);
@@ -79,6 +80,18 @@ int main() {
         for (int64_t no : n_obj)
             for (int64_t np : n_points)
                 for (int64_t ml : max_len) check_layout(z, masks[m], no, np, ml);
+    // the 2-D GP's regions at the table's slab bytes: slabs x matrix x 8 for a tier in global scratch, nothing for one in LDS
+    {
+        WsSizes zt = z;
+        for (int k = 0; k < kGpNumTiers; ++k) {
+            const GpTierRow& r = kGpTierTable[k];
+            zt.gp_slab[k] = gp_tier_slab_bytes(k);
+            CHECK(zt.gp_slab[k] == (r.global_k ? (size_t)r.slabs * gp_store_doubles(r.np) * 8 : 0), "slab bytes of tier %d", k);
+        }
+        static_assert(WS_GP_TIER_LAST + 1 == WS_BAZIN_ROWS && kGpNumTiers == 6, "one region per tier, in tier order");
+        for (int64_t ml : max_len) check_layout(zt, 0xff, 1000, 120000, ml);
+        check_layout(zt, 1 << SET_BAZIN, 1000, 120000, 768);
+    }
     // one layout by hand: Bazin alone, 7 light curves, 63 rows
     {
         const WsLayout L(z, 1 << SET_BAZIN, 7, 63, 100, true);

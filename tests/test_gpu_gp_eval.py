@@ -56,14 +56,15 @@ def device_eval(probe, np_, evals):
 
 def test_probe_instantiates_the_product_tiers(probe):
     assert probe.lib.devprobe_gp_tiers() == len(ref.TIERS)
-    info = np.zeros(5, np.int32)
+    info = np.zeros(6, np.int32)
     got = []
     for ti in range(len(ref.TIERS)):
         probe.call("devprobe_gp_tier_info", ti, info)
         got.append(tuple(int(v) for v in info))
-    # (NP, threads, matrix in global scratch, fused sweep, working set in global memory): DESIGN section 6
-    assert got == [(64, 256, 0, 0, 0), (112, 256, 1, 1, 0), (160, 512, 0, 0, 0), (240, 512, 1, 1, 0), (512, 512, 1, 1, 0),
-                   (768, 1024, 1, 0, 0), (2048, 1024, 1, 0, 1)]
+    # (NP, threads, matrix in global scratch, fused sweep, working set in global memory, compacted trip lists): DESIGN
+    # section 6
+    assert got == [(64, 256, 0, 0, 0, 1), (112, 256, 1, 1, 0, 0), (160, 512, 0, 0, 0, 1), (240, 512, 1, 1, 0, 0),
+                   (512, 512, 1, 1, 0, 1), (768, 1024, 1, 0, 0, 0), (2048, 1024, 1, 0, 1, 0)]
 
 
 @pytest.mark.parametrize("np_", ref.TIERS)
