@@ -123,10 +123,7 @@ struct SetLaunch {
     const BatchView& B;
     const Bins& bins;
     int64_t max_len;
-    double* out;
-    int ld, col0;
-    int32_t* status;
-    int st_ld, st0;
+    SetOut O;
     hipStream_t stream;
     int dev;
     int* n_launch;
@@ -139,7 +136,7 @@ struct SetLaunch {
     int launch_gp(const hipStream_t* gs, int ngs, double* const* kslab) const;
     int launch_gp1d(double* kslab) const;
     template <int SET> int launch_set() const;
-    // single launches (launch_grid): they spread the fields above into the kernel's arguments
+    // single launches (launch_grid) with the fields above as the kernel's arguments
     template <int SET, int CAP> int tier(int bin, int nan_from, hipStream_t q, unsigned long long* tk, int64_t cap = 0) const;
     template <int SET> int long_tier(int l0, int l1, int l2) const;
     template <int CAP> int stat_lean(int bin, hipStream_t q, unsigned long long* tk, int64_t cap = 0) const;
@@ -195,18 +192,13 @@ __global__ __launch_bounds__(kBinThreads) void bin_kernel(const int64_t* offsets
 
 // NaN rows + status -100 for the objects of bins [from, kNumBins) of group `g` (too long for the
 // tiers this launch sequence covers); every block of the last tier's launch takes a share.
+// (the view by value: behind a reference gp_kernel<512> spilled three registers more)
 template <class W>
-__device__ void nan_fill_bins(const Bins& bins, int g, int from, double* out, int ld, int col0, int ncol,
-                              int32_t* status, int st_ld, int st0, int nst) {
+__device__ void nan_fill_bins(const Bins& bins, int g, int from, SetOut O, int ncol, int nst) {
     for (int b = from; b < kNumBins; ++b) {
         const int c = bins.count(tier_list(g, b));
         const int* list = bins.list(tier_list(g, b));
-        for (int pos = blockIdx.x; pos < c; pos += gridDim.x) {
-            const int64_t i = list[pos];
-            fill_row_nan<W>(out + i * (int64_t)ld + col0, ncol);
-            if (status && nst)
-                for (int k = threadIdx.x; k < nst; k += blockDim.x) status[i * (int64_t)st_ld + st0 + k] = -100;
-        }
+        for (int pos = blockIdx.x; pos < c; pos += gridDim.x) O.unavailable<W>(list[pos], ncol, nst);
     }
 }
 
@@ -222,9 +214,8 @@ __device__ void nan_fill_bins(const Bins& bins, int g, int from, double* out, in
 template <int SET, int CAP> struct set_waves { static constexpr int N = (CAP <= 128) ? SetTraits<SET>::waves128 : 1; };
 
 template <int SET, int CAP>
-__global__ __launch_bounds__(64, (set_waves<SET, CAP>::N)) void set_kernel(BatchView B, Bins bins, int bin, int nan_from, double* out,
-                                                 int ld, int col0, int32_t* status, int st_ld,
-                                                 int st0, unsigned long long* ticket, int chunk) {
+__global__ __launch_bounds__(64, (set_waves<SET, CAP>::N)) void set_kernel(BatchView B, Bins bins, int bin, int nan_from, SetOut O,
+                                                 unsigned long long* ticket, int chunk) {
     __shared__ SetLds<SET, CAP> ws;
     __shared__ long long next_ticket;
     using W = WaveDev;
@@ -244,9 +235,9 @@ __global__ __launch_bounds__(64, (set_waves<SET, CAP>::N)) void set_kernel(Batch
         tc.load(list, base, nk, B);
         for (int k = 0; k < nk; ++k) {
             const auto [i, s, n] = tc.object(k);
-            double* row = out + i * (int64_t)ld + col0;
-            int32_t* st = (status && nst) ? status + i * (int64_t)st_ld + st0 : nullptr;
-            ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n, B.z ? B.z[i] : qnan()};
+            double* row = O.row(i);
+            int32_t* st = nst ? O.st(i) : nullptr;
+            const ObjIn in = B.object(i, s, n, true);
             LCFE_PT(5);
             const int rc = RunSet<W, SET, CAP>::run(in, ws, row, st);
             if constexpr (SetTraits<SET>::overflow_list >= 0) {
@@ -257,7 +248,7 @@ __global__ __launch_bounds__(64, (set_waves<SET, CAP>::N)) void set_kernel(Batch
             LCFE_PT0B();
         }
     }
-    nan_fill_bins<W>(bins, 0, nan_from, out, ld, col0, ncol, status, st_ld, st0, nst);
+    nan_fill_bins<W>(bins, 0, nan_from, O, ncol, nst);
     LCFE_PT(5);
     LCFE_PT_FLUSH();
 }
@@ -269,7 +260,7 @@ __global__ __launch_bounds__(64, (set_waves<SET, CAP>::N)) void set_kernel(Batch
 template <int CAP> struct stat_lean_waves { static constexpr int N = (CAP <= 128) ? 4 : ((CAP <= 256) ? 3 : 2); };
 
 template <int CAP>
-__global__ __launch_bounds__(64, stat_lean_waves<CAP>::N) void stat_lean_kernel(BatchView B, Bins bins, int bin, double* out, int ld, int col0,
+__global__ __launch_bounds__(64, stat_lean_waves<CAP>::N) void stat_lean_kernel(BatchView B, Bins bins, int bin, SetOut O,
                                                        unsigned long long* ticket, int chunk) {
     __shared__ StatLeanLds<CAP> L;
     __shared__ long long next_ticket;
@@ -289,14 +280,14 @@ __global__ __launch_bounds__(64, stat_lean_waves<CAP>::N) void stat_lean_kernel(
         tc.load(list, base, nk, B);
         for (int k = 0; k < nk; ++k) {
             const auto [obj, s, n] = tc.object(k);
-            ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n, qnan()};
+            const ObjIn in = B.object(obj, s, n, false);
             LCFE_PT(5);
             const bool lean = stat_lean_stage<CAP>(in, L);
             LCFE_PT(0);
             if (lean) {
                 stat_lean_object<CAP>((int)n, L);
                 LCFE_PT0B();
-                store_row<W>(L.out, out + obj * ld + col0, STAT_NCOL);
+                store_row<W>(L.out, O.row(obj), STAT_NCOL);
                 W::sync();
                 LCFE_PT(3);
             } else if (threadIdx.x == 0) bins.append(kStatFallbackList, (int)obj);
@@ -318,8 +309,8 @@ constexpr int kLongGrid = 16;
 template <int SET> constexpr size_t long_slab_bytes() { return (sizeof(SetLds<SET, kLongCap>) + 255) & ~(size_t)255; }
 
 template <int SET>
-__global__ __launch_bounds__(64) void set_long_kernel(BatchView B, Bins bins, int l0, int l1, int l2, double* out, int ld, int col0,
-                                                      int32_t* status, int st_ld, int st0, unsigned long long* ticket, char* slabs) {
+__global__ __launch_bounds__(64) void set_long_kernel(BatchView B, Bins bins, int l0, int l1, int l2, SetOut O,
+                                                      unsigned long long* ticket, char* slabs) {
     using W = LongDev;
     __shared__ long long next_ticket;
     SetLds<SET, kLongCap>& ws = *reinterpret_cast<SetLds<SET, kLongCap>*>(slabs + (size_t)blockIdx.x * long_slab_bytes<SET>());
@@ -331,12 +322,14 @@ __global__ __launch_bounds__(64) void set_long_kernel(BatchView B, Bins bins, in
         const int li = (pos < c0) ? l0 : ((pos < (int64_t)c0 + c1) ? l1 : l2);
         const int64_t at = (pos < c0) ? pos : ((pos < (int64_t)c0 + c1) ? pos - c0 : pos - c0 - c1);
         const auto [i, s, n] = take_object(B, bins.list(li), at);
-        double* row = out + i * (int64_t)ld + col0;
-        int32_t* st = (status && nst) ? status + i * (int64_t)st_ld + st0 : nullptr;
+        double* row = O.row(i);
+        int32_t* st = nst ? O.st(i) : nullptr;
         if (n <= kLongCap) {
-            ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n, B.z ? B.z[i] : qnan()};
+            const ObjIn in = B.object(i, s, n, true);
             RunSet<W, SET, kLongCap>::run(in, ws, row, st);
         } else {
+            // (O.unavailable spelled out on the two addresses above: rebuilt from i and the view in this branch they
+            //  cost set_long_kernel<9>, <12> two or three VGPRs and <2>, at 255 VGPRs, two AGPRs)
             fill_row_nan<W>(row, ncol);
             if (st) for (int k = threadIdx.x; k < nst; k += 64) st[k] = -100;
         }
@@ -347,7 +340,7 @@ __global__ __launch_bounds__(64) void set_long_kernel(BatchView B, Bins bins, in
 // (the set's eighth ticket counter; the callers have checked that the workspace holds the slabs)
 template <int SET>
 int SetLaunch::long_tier(int l0, int l1, int l2) const {
-    hipLaunchKernelGGL(set_long_kernel<SET>, dim3(kLongGrid), dim3(64), 0, stream, B, bins, l0, l1, l2, out, ld, col0, status, st_ld, st0,
+    hipLaunchKernelGGL(set_long_kernel<SET>, dim3(kLongGrid), dim3(64), 0, stream, B, bins, l0, l1, l2, O,
                        tickets + SetTraits<SET>::ticket_base + 7, long_slabs);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -387,22 +380,21 @@ constexpr bool stat_route_takes(int list, int n, int eff) {
 // Batch `b`, numbered from route R's first: route R's if its list has that many batches, else the next route's.
 template <int R>
 __device__ __forceinline__ void stat_lanes_route(int b, const int (&count)[kStatLanesRoutes], const BatchView& B, const Bins& bins, LanesBuf lbuf,
-                                                 LanesBuf lall, double* out, int ld, int col0, int retry) {
+                                                 LanesBuf lall, const SetOut& O, int retry) {
     if constexpr (R < kStatLanesRoutes) {
         constexpr StatLanesRoute r = kStatLanesRoute[R];
         const int nb = (count[R] + r.batch() - 1) / r.batch();
         if (b < nb) {
-            stat_lanes_run<r.lpo, r.cap, r.iters>(B.offsets, B.t, B.f, B.e, B.b, bins.list(r.list), count[R], b, lbuf, lall, out, ld, col0, bins,
-                                                  retry);
+            stat_lanes_run<r.lpo, r.cap, r.iters>(B.offsets, B.t, B.f, B.e, B.b, bins.list(r.list), count[R], b, lbuf, lall, O, bins, retry);
             return;
         }
-        stat_lanes_route<R + 1>(b - nb, count, B, bins, lbuf, lall, out, ld, col0, retry);
+        stat_lanes_route<R + 1>(b - nb, count, B, bins, lbuf, lall, O, retry);
     }
 }
 #ifdef LCFE_DEBUG
 constexpr double kLanesCanary = 0x1.5ca1ab1edeadp+900;
 #endif
-__global__ __launch_bounds__(64, 2) void stat_lanes_all_kernel(BatchView B, Bins bins, int retry, double* out, int ld, int col0) {
+__global__ __launch_bounds__(64, 2) void stat_lanes_all_kernel(BatchView B, Bins bins, int retry, SetOut O) {
 #ifdef LCFE_DEBUG
     // debug build: canary words around the buffers, verified when the workgroup's batch is done
     struct Framed { double pre[8]; StatLanesLds<kStatLanesMaxCap> L; double post[8]; };
@@ -430,7 +422,7 @@ __global__ __launch_bounds__(64, 2) void stat_lanes_all_kernel(BatchView B, Bins
     const int count[kStatLanesRoutes] = {bins.count(kStatLanesRoute[0].list), bins.count(kStatLanesRoute[1].list),
                                          bins.count(kStatLanesRoute[2].list), bins.count(kStatLanesRoute[3].list),
                                          bins.count(kStatLanesRoute[4].list)};
-    stat_lanes_route<0>((int)blockIdx.x, count, B, bins, lbuf, lall, out, ld, col0, retry);
+    stat_lanes_route<0>((int)blockIdx.x, count, B, bins, lbuf, lall, O, retry);
 }
 
 // Which statistics kernel takes a light curve of up to 512 rows: ONE launch over the three tier lists (128 / 256 / 512
@@ -597,8 +589,7 @@ static_assert(16 * sizeof(FitRegionNarrow) <= 8 * sizeof(FitRegion<32>), "the na
 
 // partition pass: one object per wavefront (tier lists of the feature sets), up to `chunk` objects per ticket
 template <int CAP>
-__global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bins bins, int bin, int nan_from, FitWs F, double* out, int ld,
-                                                                int col0, int32_t* status, int st_ld, int st0,
+__global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bins bins, int bin, int nan_from, FitWs F, SetOut O,
                                                                 unsigned long long* ticket, int chunk, int narrow) {
     __shared__ ObjLds<CAP> L;
     __shared__ long long next_ticket;
@@ -616,7 +607,7 @@ __global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bin
             const int64_t i = list[base + k];
             const int64_t s = B.offsets[i];
             const int n = (int)(B.offsets[i + 1] - s);
-            ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, n, qnan()};
+            const ObjIn in = B.object(i, s, n, false);
             stage_object<W, CAP>(in, L);
             const int nb = L.boff[6];
             for (int q = threadIdx.x; q < nb; q += 64) { F.pt[s + q] = L.bt[q]; F.pf[s + q] = L.bf[q]; F.pe[s + q] = L.be[q]; }
@@ -631,17 +622,16 @@ __global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bin
                     if (threadIdx.x == 0) bins.append(kBazinFallbackList, (int)i);
                 } else {
                     // the long-object tier takes it (when the caller's workspace has its slabs); NaN and -100 until then
-                    fill_row_nan<W>(out + i * (int64_t)ld + col0, BAZIN_NCOL);
-                    if (status && threadIdx.x < 12) status[i * (int64_t)st_ld + st0 + threadIdx.x] = -100;
+                    O.unavailable<W>(i, BAZIN_NCOL, SetTraits<SET_BAZIN>::nstatus);
                     if (threadIdx.x == 0) bins.append(kBazinLongList, (int)i);
                 }
             } else if (threadIdx.x < 6) {
                 const int b = threadIdx.x;
                 const int m = L.boff[b + 1] - L.boff[b];
                 if (m < 5) {                                                    // bazin_fitting.py:76-87
-                    double* o8 = out + i * (int64_t)ld + col0 + 8 * b;
+                    double* o8 = O.row(i) + 8 * b;
                     for (int q = 0; q < 8; ++q) o8[q] = qnan();
-                    if (status) { status[i * (int64_t)st_ld + st0 + 2 * b] = TRF_FAIL_TOO_FEW; status[i * (int64_t)st_ld + st0 + 2 * b + 1] = 0; }
+                    if (int32_t* st = O.st(i)) { st[2 * b] = TRF_FAIL_TOO_FEW; st[2 * b + 1] = 0; }
                 } else {
                     const int tier = fit_tier_of(m, narrow);
                     const int slot = atomicAdd(&nloc[tier], 1);                 // LDS atomic: order inside a chunk is free
@@ -658,7 +648,7 @@ __global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bin
                 if (base_of[tr] + q < F.fit_stride) F.fits[tr * F.fit_stride + base_of[tr] + q] = loc[tr][q];
         __syncthreads();
     }
-    nan_fill_bins<W>(bins, 0, nan_from, out, ld, col0, BAZIN_NCOL, status, st_ld, st0, 12);
+    nan_fill_bins<W>(bins, 0, nan_from, O, BAZIN_NCOL, SetTraits<SET_BAZIN>::nstatus);
 }
 
 enum { FIT_IDLE = 3, FIT_EXIT = 4 };      // beside TRF_PH_OUTER / INNER / DONE
@@ -678,8 +668,8 @@ __device__ __forceinline__ int fit_narrow_first_blocks(int count_narrow, int cou
 
 // the flat loop of one list: G = lane group of one fit, NG groups of the wave take fits, Region = their LDS regions
 template <class G, int NG, class Region>
-__device__ __forceinline__ void bazin_fit_loop(Region* R, const BatchView& B, const FitWs& F, const int* list, int count, double* out, int ld,
-                                               int col0, int32_t* status, int st_ld, int st0, unsigned long long* ticket) {
+__device__ __forceinline__ void bazin_fit_loop(Region* R, const BatchView& B, const FitWs& F, const int* list, int count, const SetOut& O,
+                                               unsigned long long* ticket) {
     static_assert(NG <= G::NGROUPS, "one region per lane group");
     Region& Rg = R[(G::group_id() < NG) ? G::group_id() : 0];
     TrfView<5> V;
@@ -714,10 +704,11 @@ __device__ __forceinline__ void bazin_fit_loop(Region* R, const BatchView& B, co
         if (Z.phase == TRF_PH_OUTER) trf_outer<G, BazinModel, TrfView<5>>(m, Z, V);
         if (Z.phase == TRF_PH_INNER) trf_inner<G, BazinModel, TrfView<5>>(BazinModel(), F.pt + src, F.pf + src, m, Z, V);
         if (Z.phase == TRF_PH_DONE) {
-            bazin_finish<G>(F.pt + src, F.pf + src, F.pe + src, m, Z, out + obj * (int64_t)ld + col0 + 8 * band);
-            if (status && gl == 0) {
-                status[obj * (int64_t)st_ld + st0 + 2 * band] = Z.res.status;
-                status[obj * (int64_t)st_ld + st0 + 2 * band + 1] = Z.res.nfev;
+            bazin_finish<G>(F.pt + src, F.pf + src, F.pe + src, m, Z, O.row(obj) + 8 * band);
+            int32_t* st = O.st(obj);
+            if (st && gl == 0) {
+                st[2 * band] = Z.res.status;
+                st[2 * band + 1] = Z.res.nfev;
             }
             G::sync();
             Z.phase = FIT_IDLE;
@@ -728,9 +719,8 @@ __device__ __forceinline__ void bazin_fit_loop(Region* R, const BatchView& B, co
 // list `tier` (bands of up to BCAP rows); the 32-row kernel also serves list 0 (up to 16 rows, 4-lane groups): a kernel
 // of its own behind the other four would add its longest fit to the end of the fit stream
 template <int BCAP>
-__global__ __launch_bounds__(64, (fit_waves<BCAP>::N)) void bazin_fit_kernel(BatchView B, Bins bins, FitWs F, int tier, double* out, int ld, int col0,
-                                                            int32_t* status, int st_ld, int st0, unsigned long long* ticket,
-                                                            unsigned long long* ticket_narrow) {
+__global__ __launch_bounds__(64, (fit_waves<BCAP>::N)) void bazin_fit_kernel(BatchView B, Bins bins, FitWs F, int tier, SetOut O,
+                                                            unsigned long long* ticket, unsigned long long* ticket_narrow) {
     constexpr int NG = fit_groups<BCAP>::N;
     const int count = bins.counts[kFitCountBase + tier];
     const int* list = F.fits + (int64_t)tier * F.fit_stride;
@@ -740,24 +730,24 @@ __global__ __launch_bounds__(64, (fit_waves<BCAP>::N)) void bazin_fit_kernel(Bat
         const bool narrow_first = (int)blockIdx.x < fit_narrow_first_blocks(count_n, count);
         for (int pass = 0; pass < 2; ++pass) {
             if ((pass == 0) == narrow_first) {
-                if (count_n > 0) bazin_fit_loop<GroupDev<4>, 16>(R.narrow, B, F, F.fits, count_n, out, ld, col0, status, st_ld, st0, ticket_narrow);
+                if (count_n > 0) bazin_fit_loop<GroupDev<4>, 16>(R.narrow, B, F, F.fits, count_n, O, ticket_narrow);
             } else {
-                if (count > 0) bazin_fit_loop<GroupDev<8>, NG>(R.wide, B, F, list, count, out, ld, col0, status, st_ld, st0, ticket);
+                if (count > 0) bazin_fit_loop<GroupDev<8>, NG>(R.wide, B, F, list, count, O, ticket);
             }
             __syncthreads();
         }
     } else {
         __shared__ FitRegion<BCAP> R[NG];
-        bazin_fit_loop<GroupDev<8>, NG>(R, B, F, list, count, out, ld, col0, status, st_ld, st0, ticket);
+        bazin_fit_loop<GroupDev<8>, NG>(R, B, F, list, count, O, ticket);
     }
 }
 
 // the four cross-band columns of every object (bazin_fitting.py:217-249) once all its fits are in
-__global__ __launch_bounds__(256) void bazin_cross_kernel(BatchView B, double* out, int ld, int col0) {
+__global__ __launch_bounds__(256) void bazin_cross_kernel(BatchView B, SetOut O) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= B.n_obj) return;
     double o[BAZIN_NCOL];
-    double* row = out + i * (int64_t)ld + col0;
+    double* row = O.row(i);
     for (int k = 0; k < 48; ++k) o[k] = row[k];
     bazin_cross_band(o);
     for (int k = 48; k < 52; ++k) row[k] = o[k];
@@ -790,8 +780,7 @@ struct PlRegion {
 };
 
 template <int CAP>
-__global__ __launch_bounds__(64, 2) void powerlaw_partition_kernel(BatchView B, Bins bins, int bin, int nan_from, PlWs F, double* out, int ld,
-                                                                   int col0, int32_t* status, int st_ld, int st0,
+__global__ __launch_bounds__(64, 2) void powerlaw_partition_kernel(BatchView B, Bins bins, int bin, int nan_from, PlWs F, SetOut O,
                                                                    unsigned long long* ticket, int chunk, int narrow) {
     __shared__ ObjLds<CAP> L;
     __shared__ long long next_ticket;
@@ -807,7 +796,7 @@ __global__ __launch_bounds__(64, 2) void powerlaw_partition_kernel(BatchView B, 
             const int64_t i = list[base + q];
             const int64_t s = B.offsets[i];
             const int n = (int)(B.offsets[i + 1] - s);
-            ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, n, qnan()};
+            const ObjIn in = B.object(i, s, n, false);
             stage_object<W, CAP>(in, L);
             if (threadIdx.x < 8) F.pboff[i * 8 + threadIdx.x] = L.boff[threadIdx.x];
             int kb[3];
@@ -825,18 +814,18 @@ __global__ __launch_bounds__(64, 2) void powerlaw_partition_kernel(BatchView B, 
                 if (n <= 1024) {
                     if (threadIdx.x == 0) bins.append(kPowerlawFallbackList, (int)i);
                 } else {
-                    fill_row_nan<W>(out + i * (int64_t)ld + col0, POWERLAW_NCOL);
-                    if (status && threadIdx.x < 54) status[i * (int64_t)st_ld + st0 + threadIdx.x] = -100;
+                    O.unavailable<W>(i, POWERLAW_NCOL, SetTraits<SET_POWERLAW>::nstatus);
                     if (threadIdx.x == 0) bins.append(kPowerlawLongList, (int)i);
                 }
             } else if (threadIdx.x < 3) {
                 const int j = threadIdx.x;
                 const int k = kb[j];
                 if (k < 0) {                                                    // train_v55_powerlaw.py:150-151,162-163
-                    double* o9 = out + i * (int64_t)ld + col0 + 9 * j;
+                    double* o9 = O.row(i) + 9 * j;
+                    int32_t* st = O.st(i);
                     for (int id = 0; id < 9; ++id) {
                         o9[id] = qnan();
-                        if (status) { status[i * (int64_t)st_ld + st0 + 18 * j + 2 * id] = TRF_FAIL_TOO_FEW; status[i * (int64_t)st_ld + st0 + 18 * j + 2 * id + 1] = 0; }
+                        if (st) { st[18 * j + 2 * id] = TRF_FAIL_TOO_FEW; st[18 * j + 2 * id + 1] = 0; }
                     }
                 } else {
                     const int tier = fit_tier_of(k, narrow);
@@ -853,7 +842,7 @@ __global__ __launch_bounds__(64, 2) void powerlaw_partition_kernel(BatchView B, 
             __syncthreads();
         }
     }
-    nan_fill_bins<W>(bins, 0, nan_from, out, ld, col0, POWERLAW_NCOL, status, st_ld, st0, 54);
+    nan_fill_bins<W>(bins, 0, nan_from, O, POWERLAW_NCOL, SetTraits<SET_POWERLAW>::nstatus);
 }
 
 // N = 2: the seven power laws (PowerModel, exponent from the fit id); N = 3: exponential and linear (Decline3Model)
@@ -862,8 +851,8 @@ template <> struct pl_model<2> { using type = PowerModel; static __device__ __fo
 template <> struct pl_model<3> { using type = Decline3Model; static __device__ __forceinline__ Decline3Model make(int id) { return Decline3Model{id}; } };
 
 template <class G, int N, int NG, class Region>
-__device__ __forceinline__ void powerlaw_fit_loop(Region* R, const BatchView& B, const PlWs& F, const int* list, int count, double* out, int ld,
-                                                  int col0, int32_t* status, int st_ld, int st0, unsigned long long* ticket) {
+__device__ __forceinline__ void powerlaw_fit_loop(Region* R, const BatchView& B, const PlWs& F, const int* list, int count, const SetOut& O,
+                                                  unsigned long long* ticket) {
     static_assert(NG <= G::NGROUPS, "one region per lane group");
     using M = typename pl_model<N>::type;
     Region& Rg = R[(G::group_id() < NG) ? G::group_id() : 0];
@@ -904,10 +893,11 @@ __device__ __forceinline__ void powerlaw_fit_loop(Region* R, const BatchView& B,
         if (Z.phase == TRF_PH_OUTER) trf_outer<G, M, TrfView<N>>(k, Z, V);
         if (Z.phase == TRF_PH_INNER) trf_inner<G, M, TrfView<N>>(model, Rg.t, Rg.f, k, Z, V);
         if (Z.phase == TRF_PH_DONE) {
-            decline_finish<G, M>(model, Rg.t, Rg.f, k, ss_tot, Z, out + obj * (int64_t)ld + col0 + 9 * j + id);
-            if (status && gl == 0) {
-                status[obj * (int64_t)st_ld + st0 + 18 * j + 2 * id] = Z.res.status;
-                status[obj * (int64_t)st_ld + st0 + 18 * j + 2 * id + 1] = Z.res.nfev;
+            decline_finish<G, M>(model, Rg.t, Rg.f, k, ss_tot, Z, O.row(obj) + 9 * j + id);
+            int32_t* st = O.st(obj);
+            if (st && gl == 0) {
+                st[18 * j + 2 * id] = Z.res.status;
+                st[18 * j + 2 * id + 1] = Z.res.nfev;
             }
             G::sync();
             Z.phase = FIT_IDLE;
@@ -917,8 +907,7 @@ __device__ __forceinline__ void powerlaw_fit_loop(Region* R, const BatchView& B,
 
 // list `tier` of the N-parameter models; the 32-row kernel also serves list 0 on 4-lane groups (see bazin_fit_kernel)
 template <int N, int BCAP>
-__global__ __launch_bounds__(64, (BCAP <= 64 ? 2 : 1)) void powerlaw_fit_kernel(BatchView B, Bins bins, PlWs F, int tier, double* out, int ld,
-                                                                                  int col0, int32_t* status, int st_ld, int st0,
+__global__ __launch_bounds__(64, (BCAP <= 64 ? 2 : 1)) void powerlaw_fit_kernel(BatchView B, Bins bins, PlWs F, int tier, SetOut O,
                                                                                   unsigned long long* ticket, unsigned long long* ticket_narrow) {
     constexpr int NG = fit_groups<BCAP>::N;
     constexpr int kCount = (N == 2) ? kPlCountA : kPlCountB;
@@ -931,15 +920,15 @@ __global__ __launch_bounds__(64, (BCAP <= 64 ? 2 : 1)) void powerlaw_fit_kernel(
         const bool narrow_first = (int)blockIdx.x < fit_narrow_first_blocks(count_n, count);
         for (int pass = 0; pass < 2; ++pass) {
             if ((pass == 0) == narrow_first) {
-                if (count_n > 0) powerlaw_fit_loop<GroupDev<4>, N, 16>(R.narrow, B, F, lists, count_n, out, ld, col0, status, st_ld, st0, ticket_narrow);
+                if (count_n > 0) powerlaw_fit_loop<GroupDev<4>, N, 16>(R.narrow, B, F, lists, count_n, O, ticket_narrow);
             } else {
-                if (count > 0) powerlaw_fit_loop<GroupDev<8>, N, NG>(R.wide, B, F, list, count, out, ld, col0, status, st_ld, st0, ticket);
+                if (count > 0) powerlaw_fit_loop<GroupDev<8>, N, NG>(R.wide, B, F, list, count, O, ticket);
             }
             __syncthreads();
         }
     } else {
         __shared__ PlRegion<N, BCAP> R[NG];
-        powerlaw_fit_loop<GroupDev<8>, N, NG>(R, B, F, list, count, out, ld, col0, status, st_ld, st0, ticket);
+        powerlaw_fit_loop<GroupDev<8>, N, NG>(R, B, F, list, count, O, ticket);
     }
 }
 
@@ -948,9 +937,8 @@ __global__ __launch_bounds__(64, (BCAP <= 64 ? 2 : 1)) void powerlaw_fit_kernel(
 // global scratch.  Objects come from the tier's index list through a ticket counter (one object per
 // ticket: an L-BFGS-B run is 10^5..10^7 cycles and heavy-tailed).
 template <int NP, bool GLOBAL_K>
-__global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP>::N)) void gp_kernel(BatchView B, Bins bins, int bin, int nan_from, double* out, int ld,
-                                                 int col0, int32_t* status, int st_ld, int st0, double* kscratch,
-                                                 unsigned long long* ticket) {
+__global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP>::N)) void gp_kernel(BatchView B, Bins bins, int bin, int nan_from, SetOut O,
+                                                 double* kscratch, unsigned long long* ticket) {
     using Tier = GpTier<NP, GLOBAL_K>;
     using W = typename Tier::W;
     __shared__ typename Tier::Set S;
@@ -963,20 +951,19 @@ __global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP>::N)) void gp_kerne
         const int64_t pos = block_ticket(ticket, next_ticket);
         if (pos >= count) break;
         const auto [i, s, n64] = take_object(B, list, pos);
-        double* row = out + i * (int64_t)ld + col0;
-        int32_t* st = status ? status + i * (int64_t)st_ld + st0 : nullptr;
-        ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n64, qnan()};
+        double* row = O.row(i);
+        int32_t* st = O.st(i);
+        const ObjIn in = B.object(i, s, n64, false);
         gp_object<W, NP>(in, S, [&](const double* x, int n, double& f, double* g, bool need) {
             Tier::eval(S, Tier::matrix(Klds, Kg), x, n, f, g, need); }, st);
         store_row<W>(S.out, row, GP_NCOL);
         __syncthreads();
     }
-    nan_fill_bins<W>(bins, 1, nan_from, out, ld, col0, GP_NCOL, status, st_ld, st0, 4);
+    nan_fill_bins<W>(bins, 1, nan_from, O, GP_NCOL, 4);
 }
 
 // the same loop for the long-object tier (slabs: GpLongTier::kBytes)
-__global__ __launch_bounds__(kGpLongThreads, 1) void gp_long_kernel(BatchView B, Bins bins, int bin, double* out, int ld, int col0,
-                                                                   int32_t* status, int st_ld, int st0, char* slabs,
+__global__ __launch_bounds__(kGpLongThreads, 1) void gp_long_kernel(BatchView B, Bins bins, int bin, SetOut O, char* slabs,
                                                                    unsigned long long* ticket) {
     using Tier = GpLongTier;
     using W = Tier::W;
@@ -990,10 +977,10 @@ __global__ __launch_bounds__(kGpLongThreads, 1) void gp_long_kernel(BatchView B,
         const int64_t pos = block_ticket(ticket, next_ticket);
         if (pos >= count) break;
         const auto [i, s, n64] = take_object(B, list, pos);
-        int32_t* st = status ? status + i * (int64_t)st_ld + st0 : nullptr;
-        ObjIn in{B.t + s, B.f + s, B.e + s, B.b + s, (int)n64, qnan()};
+        int32_t* st = O.st(i);
+        const ObjIn in = B.object(i, s, n64, false);
         gp_object<W, NP>(in, S, [&](const double* x, int n, double& f, double* g, bool need) { Tier::eval(S, Kg, x, n, f, g, need); }, st);
-        store_row<W>(S.out, out + i * (int64_t)ld + col0, GP_NCOL);
+        store_row<W>(S.out, O.row(i), GP_NCOL);
         __syncthreads();
     }
 }
@@ -1054,8 +1041,8 @@ int SetLaunch::gp_tier(int ti, int nan_from, hipStream_t q, double* kscratch, in
         const char* e = getenv(name);
         if (e && atoi(e) > 0 && (cap < 1 || atoi(e) < cap)) cap = atoi(e);
     }
-    return launch_grid(gp_kernel<NP, GLOBAL_K>, gp_threads<NP>::T, {0, cap}, B.n_obj, 1, q, dev, B, bins, ti, nan_from, out, ld, col0, status,
-                       st_ld, st0, kscratch, tickets + SET_GP2D * 8 + ti);
+    return launch_grid(gp_kernel<NP, GLOBAL_K>, gp_threads<NP>::T, {0, cap}, B.n_obj, 1, q, dev, B, bins, ti, nan_from, O, kscratch,
+                       tickets + SET_GP2D * 8 + ti);
 }
 
 // kslab[tier]: the tier's Gram-matrix slabs (WS_GP_TIER + tier; no bytes behind the pointer of a tier whose matrix is in LDS)
@@ -1118,8 +1105,8 @@ int SetLaunch::launch_gp(const hipStream_t* gs, int ngs, double* const* kslab) c
         ++*n_launch;
         // light curves beyond the last tier's cap (bin 6; NaN rows and status -100 from the launch above until this one has run)
         if (ti == last && last == kGpNumTiers - 1 && long_slabs) {
-            hipLaunchKernelGGL(gp_long_kernel, dim3(kGpLongGrid), dim3(kGpLongThreads), 0, q, B, bins, kGpNumTiers, out, ld, col0, status,
-                               st_ld, st0, long_slabs, tickets + SET_GP2D * 8 + 7);
+            hipLaunchKernelGGL(gp_long_kernel, dim3(kGpLongGrid), dim3(kGpLongThreads), 0, q, B, bins, kGpNumTiers, O, long_slabs,
+                               tickets + SET_GP2D * 8 + 7);
             HIP_TRY(hipGetLastError());
             ++*n_launch;
         }
@@ -1141,8 +1128,7 @@ __device__ __forceinline__ void gp1d_fit_band(const Rows& R, int j, const double
 
 // MW = waves per SIMD the register allocation leaves room for (= workgroups per CU at 256 threads)
 template <int NP, int ROWCAP, int T, int WNP, int MW>
-__global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int bin, int nan_from, double* out, int ld,
-                                                   int col0, int32_t* status, int st_ld, int st0,
+__global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int bin, int nan_from, SetOut O,
                                                    unsigned long long* ticket, double* kslab) {
     using W = BlockDev<T>;
     constexpr bool kWavePath = (T == 256);
@@ -1161,7 +1147,7 @@ __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int
         const double* t = B.t + s;
         const double* f = B.f + s;
         const double* e = B.e + s;
-        int32_t* st = status ? status + i * (int64_t)st_ld + st0 : nullptr;
+        int32_t* st = O.st(i);
         R.build(t, f, e, B.b + s, (int)o.n);
         auto nvalid = [&](int j) { return R.boff[j + 1] - R.boff[j]; };
         bool fitted[4];
@@ -1202,24 +1188,23 @@ __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int
         __syncthreads();
         if (threadIdx.x == 0) gp1d_cross_band(orow, fitted);
         __syncthreads();
-        store_row<W>(orow, out + i * (int64_t)ld + col0, GP1D_NCOL);
+        store_row<W>(orow, O.row(i), GP1D_NCOL);
         __syncthreads();
     }
-    nan_fill_bins<W>(bins, 1, nan_from, out, ld, col0, GP1D_NCOL, status, st_ld, st0, GP1D_NSTATUS);
+    nan_fill_bins<W>(bins, 1, nan_from, O, GP1D_NCOL, GP1D_NSTATUS);
 }
 
 // (kslab: one slab of global scratch per workgroup)
 template <int NP, int ROWCAP, int T, int WNP, int MW>
 int SetLaunch::gp1d_tier(int ti, int nan_from, double* kslab) const {
-    return launch_grid(gp1d_kernel<NP, ROWCAP, T, WNP, MW>, T, {0, kslab ? kGp1dLongGrid : 0}, B.n_obj, 1, stream, dev, B, bins, ti, nan_from, out,
-                       ld, col0, status, st_ld, st0, tickets + SET_GP1D * 8 + ti, kslab);
+    return launch_grid(gp1d_kernel<NP, ROWCAP, T, WNP, MW>, T, {0, kslab ? kGp1dLongGrid : 0}, B.n_obj, 1, stream, dev, B, bins, ti, nan_from, O,
+                       tickets + SET_GP1D * 8 + ti, kslab);
 }
 
 // ---- the long-object tier of the per-band GP (gp1d_tiers.hpp)
 // slabs: kGp1dLongTierGrid Gram matrices, then kGp1dLongTierGrid working sets.  Light curves of more than kLongCap rows keep
 // the NaN row and status -100 the tier-5 launch wrote.
-__global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B, Bins bins, double* out, int ld, int col0, int32_t* status,
-                                                                   int st_ld, int st0, char* slabs, unsigned long long* ticket) {
+__global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B, Bins bins, SetOut O, char* slabs, unsigned long long* ticket) {
     constexpr int T = kGp1dThreads, NP = kGp1dLongTierNP;
     using W = BlockDev<T>;
     // valid rows of g, r, i, z, partitioned by band, each part in time order; the rank sort takes the bands the fit takes
@@ -1240,7 +1225,7 @@ __global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B,
             const double* t = B.t + s;
             const double* f = B.f + s;
             const double* e = B.e + s;
-            int32_t* st = status ? status + i * (int64_t)st_ld + st0 : nullptr;
+            int32_t* st = O.st(i);
             R.build(t, f, e, B.b + s, (int)o.n);
             bool fitted[4];
 #pragma unroll
@@ -1251,7 +1236,7 @@ __global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B,
             }
             if (threadIdx.x == 0) gp1d_cross_band(orow, fitted);
             __syncthreads();
-            store_row<W>(orow, out + i * (int64_t)ld + col0, GP1D_NCOL);
+            store_row<W>(orow, O.row(i), GP1D_NCOL);
         }
         __syncthreads();
     }
@@ -1280,8 +1265,8 @@ int SetLaunch::launch_gp1d(double* kslab) const {
     // ran before them on this stream.  Last on the stream, so that the short tiers do not wait for 8 workgroups that may
     // take seconds per light curve.
     if (long_slabs && max_len > SetTraits<SET_GP1D>::long_above) {
-        hipLaunchKernelGGL(gp1d_long_kernel, dim3(kGp1dLongTierGrid), dim3(kGp1dThreads), 0, stream, B, bins, out, ld, col0, status,
-                           st_ld, st0, long_slabs, tickets + SET_GP1D * 8 + 7);
+        hipLaunchKernelGGL(gp1d_long_kernel, dim3(kGp1dLongTierGrid), dim3(kGp1dThreads), 0, stream, B, bins, O, long_slabs,
+                           tickets + SET_GP1D * 8 + 7);
         HIP_TRY(hipGetLastError());
         ++*n_launch;
     }
@@ -1291,8 +1276,7 @@ int SetLaunch::launch_gp1d(double* kslab) const {
 template <int SET, int CAP>
 int SetLaunch::tier(int bin, int nan_from, hipStream_t q, unsigned long long* tk, int64_t cap) const {
     constexpr int chunk = SetTraits<SET>::chunk;
-    return launch_grid(set_kernel<SET, CAP>, 64, {0, cap}, B.n_obj, chunk, q, dev, B, bins, bin, nan_from, out, ld, col0, status, st_ld, st0,
-                       tk, chunk);
+    return launch_grid(set_kernel<SET, CAP>, 64, {0, cap}, B.n_obj, chunk, q, dev, B, bins, bin, nan_from, O, tk, chunk);
 }
 
 template <int SET>
@@ -1340,8 +1324,8 @@ int SetLaunch::launch_bazin(const FitWs& F) const {
     unsigned long long* tk = tickets + SET_BAZIN * 8;
     for (int ti = 0; ti <= last; ++ti) {
         const int rc = for_tier(ti, [&](auto cap) {
-            return launch_grid(bazin_partition_kernel<cap()>, 64, {}, B.n_obj, 8, stream, dev, B, bins, ti, nan_from_of(ti, last), F, out, ld,
-                               col0, status, st_ld, st0, tk + ti, 8, fit_narrow_enabled() ? 1 : 0);
+            return launch_grid(bazin_partition_kernel<cap()>, 64, {}, B.n_obj, 8, stream, dev, B, bins, ti, nan_from_of(ti, last), F, O, tk + ti,
+                               8, fit_narrow_enabled() ? 1 : 0);
         });
         if (rc) return rc;
         ++*n_launch;
@@ -1356,8 +1340,7 @@ int SetLaunch::launch_bazin(const FitWs& F) const {
     unsigned long long* ftk = tickets + kFitTicketBase;
     auto fits = [&](auto t) {
         constexpr int T = t(), BCAP = kFitCaps[T];
-        return launch_grid(bazin_fit_kernel<BCAP>, 64, {fit_waves_cap(BCAP), 0}, kBazinFits * B.n_obj, 8, stream, dev, B, bins, F, T, out, ld,
-                           col0, status, st_ld, st0, ftk + T, ftk);
+        return launch_grid(bazin_fit_kernel<BCAP>, 64, {fit_waves_cap(BCAP), 0}, kBazinFits * B.n_obj, 8, stream, dev, B, bins, F, T, O, ftk + T, ftk);
     };
     rc = fits(IntTag<4>{});
     if (!rc) rc = fits(IntTag<3>{});
@@ -1365,7 +1348,7 @@ int SetLaunch::launch_bazin(const FitWs& F) const {
     if (!rc) rc = fits(IntTag<1>{});
     if (rc) return rc;
     *n_launch += 4;
-    hipLaunchKernelGGL(bazin_cross_kernel, dim3((unsigned)((B.n_obj + 255) / 256)), dim3(256), 0, stream, B, out, ld, col0);
+    hipLaunchKernelGGL(bazin_cross_kernel, dim3((unsigned)((B.n_obj + 255) / 256)), dim3(256), 0, stream, B, O);
     HIP_TRY(hipGetLastError());
     ++*n_launch;
     // the long-object tier: more than 2048 rows (bin 6), or more than 1024 rows with a band beyond the fit tiers (all 52 columns)
@@ -1382,8 +1365,8 @@ int SetLaunch::launch_powerlaw(const PlWs& F) const {
     unsigned long long* tk = tickets + SET_POWERLAW * 8;
     for (int ti = 0; ti <= last; ++ti) {
         const int rc = for_tier(ti, [&](auto cap) {
-            return launch_grid(powerlaw_partition_kernel<cap()>, 64, {}, B.n_obj, 8, stream, dev, B, bins, ti, nan_from_of(ti, last), F, out, ld,
-                               col0, status, st_ld, st0, tk + ti, 8, fit_narrow_enabled() ? 1 : 0);
+            return launch_grid(powerlaw_partition_kernel<cap()>, 64, {}, B.n_obj, 8, stream, dev, B, bins, ti, nan_from_of(ti, last), F, O, tk + ti,
+                               8, fit_narrow_enabled() ? 1 : 0);
         });
         if (rc) return rc;
         ++*n_launch;
@@ -1397,10 +1380,10 @@ int SetLaunch::launch_powerlaw(const PlWs& F) const {
     auto fits = [&](auto t) {
         constexpr int T = t(), BCAP = kFitCaps[T];
         const int ra = launch_grid(powerlaw_fit_kernel<2, BCAP>, 64, {fit_waves_cap(BCAP), 0}, kPlFitsA * B.n_obj, 8, stream, dev, B, bins, F, T,
-                                   out, ld, col0, status, st_ld, st0, tickets + kPlTicketA + T, tickets + kPlTicketA);
+                                   O, tickets + kPlTicketA + T, tickets + kPlTicketA);
         if (ra) return ra;
-        return launch_grid(powerlaw_fit_kernel<3, BCAP>, 64, {fit_waves_cap(BCAP), 0}, kPlFitsB * B.n_obj, 8, stream, dev, B, bins, F, T, out,
-                           ld, col0, status, st_ld, st0, tickets + kPlTicketB + T, tickets + kPlTicketB);
+        return launch_grid(powerlaw_fit_kernel<3, BCAP>, 64, {fit_waves_cap(BCAP), 0}, kPlFitsB * B.n_obj, 8, stream, dev, B, bins, F, T, O,
+                           tickets + kPlTicketB + T, tickets + kPlTicketB);
     };
     rc = fits(IntTag<4>{});
     if (!rc) rc = fits(IntTag<3>{});
@@ -1419,7 +1402,7 @@ int SetLaunch::launch_powerlaw(const PlWs& F) const {
 // (cap: for a list expected to be short: every wavefront's first ticket is an atomic on one counter)
 template <int CAP>
 int SetLaunch::stat_lean(int bin, hipStream_t q, unsigned long long* tk, int64_t cap) const {
-    return launch_grid(stat_lean_kernel<CAP>, 64, {0, cap}, B.n_obj, 8, q, dev, B, bins, bin, out, ld, col0, tk, 8);
+    return launch_grid(stat_lean_kernel<CAP>, 64, {0, cap}, B.n_obj, 8, q, dev, B, bins, bin, O, tk, 8);
 }
 
 int launch_stat_plan(const BatchView& B, const Bins& bins, hipStream_t stream) {
@@ -1429,9 +1412,9 @@ int launch_stat_plan(const BatchView& B, const Bins& bins, hipStream_t stream) {
     return 0;
 }
 
-int launch_stat_lanes_all(const BatchView& B, const Bins& bins, int retry, double* out, int ld, int col0, hipStream_t stream) {
+int launch_stat_lanes_all(const BatchView& B, const Bins& bins, int retry, const SetOut& O, hipStream_t stream) {
     const int64_t grid = (B.n_obj + 3) / 4 + 6;
-    hipLaunchKernelGGL(stat_lanes_all_kernel, dim3((unsigned)grid), dim3(64), 0, stream, B, bins, retry, out, ld, col0);
+    hipLaunchKernelGGL(stat_lanes_all_kernel, dim3((unsigned)grid), dim3(64), 0, stream, B, bins, retry, O);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1446,8 +1429,7 @@ static bool stat_lanes_enabled() {
 // for the lean kernels' fallback list and for the NaN rows of over-long objects.
 int SetLaunch::launch_stat(hipStream_t s1, hipStream_t s2) const {
     SetLaunch G = *this;                // the general kernel's launches: the set has no status words
-    G.status = nullptr;
-    G.st_ld = G.st0 = 0;
+    G.O = O.without_status();
     const int last = last_tier(max_len, 4);
     unsigned long long* tk = tickets + SET_STAT * 8;
     // The tier kernels are independent (disjoint objects): with side streams they are enqueued side by side, so the
@@ -1489,7 +1471,7 @@ int SetLaunch::launch_stat(hipStream_t s1, hipStream_t s2) const {
             // a light curve whose rows turn out not to ascend in time goes to the general kernel's list
             if (last >= 2) rc = stat_lean<512>(kStatRetryList, q_long, tk + 2);
             else if (last == 1) rc = stat_lean<256>(kStatRetryList, q_mid, tk + 1, 512);
-            if (!rc) rc = launch_stat_lanes_all(B, bins, kStatFallbackList, out, ld, col0, stream);
+            if (!rc) rc = launch_stat_lanes_all(B, bins, kStatFallbackList, O, stream);
             if (!rc && last < 1) rc = stat_lean<128>(kStatRetryList, stream, tk + 6, 512);
             *n_launch += 2;
         } else {
@@ -1927,7 +1909,7 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
         }
         if (prof && ne != 0) HIP_TRY(hipEventRecord(ev0[s], q));
         int nl = 0;
-        const SetLaunch A{B, bins, max_len, d_out, ld, col0, d_status, st_ld, st0, q, dev, &nl, tickets, long_slab[s]};
+        const SetLaunch A{B, bins, max_len, SetOut{d_out, ld, col0, d_status, st_ld, st0}, q, dev, &nl, tickets, long_slab[s]};
         const int rc = for_set(s, [&](auto tag) -> int {
             constexpr int SET = tag();
             if constexpr (SET == SET_STAT) return A.launch_stat(fork ? side[0] : q, fork ? side[1] : q);

@@ -387,13 +387,14 @@ __device__ __forceinline__ void lanes_merge_levels(double (&w)[CAP], LanesBuf bu
 }
 
 // 64 / LPO light curves (one per LPO-lane group: `obj` < 0 = none; CSR rows [s1, e1)) -> their 123 columns, or list
-// `fallback` of `lists` (Bins of tickets.hpp: lists.append(fallback, obj)).  ITERS = rows / LPO a light curve of the list
-// may have (band code 256 = no row -- 255 is a code a file may hold).  The rows are loaded in predicated blocks of four trips: one basic block of unconditional loads, a
+// `fallback` of `lists` (SetOut and Bins of tickets.hpp: O.row(obj), lists.append(fallback, obj); both are template
+// parameters so that this header stands without tickets.hpp for the host-compiled layout tests).  ITERS = rows / LPO a
+// light curve of the list may have (band code 256 = no row -- 255 is a code a file may hold).  The rows are loaded in predicated blocks of four trips: one basic block of unconditional loads, a
 // persistent batch loop around this function, or exec-masked element loops all made the compiler spill hundreds of
 // registers (profiles/r02_stat_instruction_budget.md).
-template <int LPO, int CAP, int ITERS, class Lists>
+template <int LPO, int CAP, int ITERS, class Out, class Lists>
 __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double* gf, const double* ge, const uint8_t* gb, int obj,
-                                                 int64_t s1, int64_t e1, LanesBuf buf, LanesBuf all_rows, double* out, int ld, int col0,
+                                                 int64_t s1, int64_t e1, LanesBuf buf, LanesBuf all_rows, const Out& O,
                                                  const Lists& lists, int fallback) {
     using L = LanesLayout<LPO>;
     using G = typename L::G;
@@ -800,7 +801,7 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
     for (int r = 0; r < 64 / LPO; ++r) {
         const int obj_r = __builtin_amdgcn_readlane(done ? obj : -1, LPO * r);
         if (obj_r >= 0) {
-            double* row = out + (int64_t)obj_r * ld + col0;
+            double* row = O.row(obj_r);
             LanesBuf src = buf + r * 128;
             row[lane] = src[lane];
             if (lane + 64 < STAT_NCOL) row[lane + 64] = src[lane + 64];
@@ -811,10 +812,10 @@ __device__ __forceinline__ void stat_lanes_batch(const double* gt, const double*
 }
 
 // One workgroup = one batch (`batch`) of 64 / LPO consecutive list entries; `buf`: 64 x (CAP + 1) doubles of LDS.
-template <int LPO, int CAP, int ITERS, class Lists>
+template <int LPO, int CAP, int ITERS, class Out, class Lists>
 __device__ __forceinline__ void stat_lanes_run(const int64_t* offsets, const double* gt, const double* gf, const double* ge,
                                                const uint8_t* gb, const int* list, int count, int batch, LanesBuf buf, LanesBuf all_rows,
-                                               double* out, int ld, int col0, const Lists& lists, int fallback) {
+                                               const Out& O, const Lists& lists, int fallback) {
     const int g = (threadIdx.x & 63) / LPO;
     const int64_t base = (int64_t)batch * (64 / LPO);
     int obj = -1;
@@ -824,7 +825,7 @@ __device__ __forceinline__ void stat_lanes_run(const int64_t* offsets, const dou
         s1 = offsets[obj];
         e1 = offsets[obj + 1];
     }
-    stat_lanes_batch<LPO, CAP, ITERS>(gt, gf, ge, gb, obj, s1, e1, buf, all_rows, out, ld, col0, lists, fallback);
+    stat_lanes_batch<LPO, CAP, ITERS>(gt, gf, ge, gb, obj, s1, e1, buf, all_rows, O, lists, fallback);
 }
 
 }  // namespace lcfe

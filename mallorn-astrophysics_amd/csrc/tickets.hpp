@@ -1,5 +1,6 @@
 // tickets.hpp -- what every persistent kernel of lcfe.hip stands on: how an index list is named and appended to, how a
-// workgroup takes its next ticket, and how the light curve behind a ticket is fetched.
+// workgroup takes its next ticket, how the light curve behind a ticket is fetched, and where its columns and status words
+// go.
 #pragma once
 #include "wave.hpp"
 #include "workspace.hpp"
@@ -14,6 +15,35 @@ struct BatchView {
     const uint8_t* b;
     const double* z;
     int64_t n_obj;
+    // rows [s, s + n) of light curve i; its redshift for the sets that read one (NaN where the caller passed none)
+    LCFE_FN ObjIn object(int64_t i, int64_t s, int64_t n, bool with_z) const {
+        return {t + s, f + s, e + s, b + s, (int)n, (with_z && z) ? z[i] : qnan()};
+    }
+};
+
+// Where one set's columns and status words go: row i of the caller's matrices, from the set's first column and word on.
+// Passed to the kernels by value, at the offsets the six loose arguments had.  Device functions that are inlined into one
+// kernel (the fit loops, the lanes routes) take it by const reference; nan_fill_bins, which many kernels share, takes it by
+// value (see there).
+struct SetOut {
+    double* out;
+    int ld, col0;
+    int32_t* status;                   // nullptr: the caller takes no status words
+    int st_ld, st0;
+    LCFE_FN double* row(int64_t i) const { return out + i * (int64_t)ld + col0; }
+    // (a set without status words asks `nst ? O.st(i) : nullptr`: st0 is then the next set's first word)
+    LCFE_FN int32_t* st(int64_t i) const { return status ? status + i * (int64_t)st_ld + st0 : nullptr; }
+    // "not available": NaN in the ncol columns, -100 in the nst status words, on every lane of policy W
+    template <class W>
+    LCFE_FN void unavailable(int64_t i, int ncol, int nst) const {
+        fill_row_nan<W>(row(i), ncol);
+        if (status && nst) {
+            int32_t* s = st(i);
+            for (int k = W::lane(); k < nst; k += W::LANES) s[k] = -100;
+        }
+    }
+    // (host side: launch_stat's view for the general kernel of a set that has no status words)
+    SetOut without_status() const { return {out, ld, col0, nullptr, 0, 0}; }
 };
 
 // The index lists (ids, count slots and the region behind them: workspace.hpp).  `k` is the same in every lane.
