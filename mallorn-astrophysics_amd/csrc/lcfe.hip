@@ -131,14 +131,14 @@ struct SetLaunch {
     char* long_slabs;
     // the five sets with launch sequences of their own, and every other set
     int launch_stat(hipStream_t s1, hipStream_t s2) const;
-    int launch_bazin(const FitWs& F) const;
-    int launch_powerlaw(const PlWs& F) const;
+    template <class Fam> int launch_fits(const typename Fam::Ws& F) const;     // BazinFits, DeclineFits
     int launch_gp(const hipStream_t* gs, int ngs, double* const* kslab) const;
     int launch_gp1d(double* kslab) const;
     template <int SET> int launch_set() const;
     // single launches (launch_grid) with the fields above as the kernel's arguments
     template <int SET, int CAP> int tier(int bin, int nan_from, hipStream_t q, unsigned long long* tk, int64_t cap = 0) const;
     template <int SET> int long_tier(int l0, int l1, int l2) const;
+    template <class K, class Ws> int fit_stream(K kernel, int tier, int fits_per_object, int ticket_base, const Ws& F) const;
     template <int CAP> int stat_lean(int bin, hipStream_t q, unsigned long long* tk, int64_t cap = 0) const;
     template <int NP, bool GLOBAL_K> int gp_tier(int ti, int nan_from, hipStream_t q, double* kscratch, int64_t cap) const;
     template <int NP, int ROWCAP, int T, int WNP, int MW> int gp1d_tier(int ti, int nan_from, double* kslab = nullptr) const;
@@ -550,11 +550,8 @@ __global__ __launch_bounds__(kPlanThreads) void stat_plan_kernel(BatchView B, Bi
 // wave-uniform scalar work that every lane of its group repeats, so a group of half the width halves it per fit, and
 // wave.hpp's virtual lanes keep every sum in the order of the 8-lane group -- the results are bit-identical.  Tier 0 has
 // no launch of its own: the kernel of the 32-row tier serves both lists (see bazin_fit_kernel).
-constexpr int kFitCaps[kFitTiers] = {16, 32, 64, 128, 256}; // rows of one band (count and ticket slots of the lists: workspace.hpp)
-// tier of a band of m rows (m <= 256); narrow == 0 queues the bands of up to 16 rows on the 32-row list (LCFE_FIT_NARROW=0)
-__device__ __forceinline__ int fit_tier_of(int m, int narrow) {
-    return (m <= 16) ? (narrow ? 0 : 1) : ((m <= 32) ? 1 : ((m <= 64) ? 2 : ((m <= 128) ? 3 : 4)));
-}
+// (The tiers -- rows, lanes per fit, groups per wave, register budgets, which tier hosts which -- and fit_tier_of, the
+// tier of a band of m rows: fit_tier_table.hpp.  The count and ticket slots of the lists: workspace.hpp.)
 struct FitWs {
     double* pt;            // band-partitioned copies of t / flux / err, indexed like the CSR arrays
     double* pf;
@@ -580,12 +577,13 @@ struct FitRegion {
 // Q^T f, the trial residual is written after that and copied to r before the next trf_outer.  The two words of the median
 // lie in A[4], which nothing uses before the first Jacobian.
 struct FitRegionNarrow {
-    double r[16], w[16];
-    double A[6][16 + 5];
+    double r[kFitNarrowRows], w[kFitNarrowRows];
+    double A[6][kFitNarrowRows + 5];
     __device__ __forceinline__ double* trial() { return A[5]; }
     __device__ __forceinline__ double* median_slot() { return A[4]; }
 };
-static_assert(16 * sizeof(FitRegionNarrow) <= 8 * sizeof(FitRegion<32>), "the narrow regions fit the LDS of the 32-row tier");
+static_assert(kFitNarrowGroups * sizeof(FitRegionNarrow) <= kFitTierTable[kFitNarrowHost].groups * sizeof(FitRegion<fit_tier_cap(kFitNarrowHost)>),
+              "the narrow regions fit the LDS of their host tier");
 
 // partition pass: one object per wavefront (tier lists of the feature sets), up to `chunk` objects per ticket
 template <int CAP>
@@ -615,10 +613,10 @@ __global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bin
             int mb = 0;
 #pragma unroll
             for (int b = 0; b < 6; ++b) { const int m = L.boff[b + 1] - L.boff[b]; mb = (m > mb) ? m : mb; }
-            if (mb > kFitCaps[kFitTiers - 1]) {
+            if (mb > kFitMaxRows) {
                 // a band beyond the largest fit tier: the whole object goes to the object-level kernel, which takes
                 // light curves of up to 1024 rows; beyond that the fit is not available (NaN, status -100)
-                if (n <= 1024) {
+                if (n <= kFitObjectRows) {
                     if (threadIdx.x == 0) bins.append(kBazinFallbackList, (int)i);
                 } else {
                     // the long-object tier takes it (when the caller's workspace has its slabs); NaN and -100 until then
@@ -652,10 +650,6 @@ __global__ __launch_bounds__(64, 2) void bazin_partition_kernel(BatchView B, Bin
 }
 
 enum { FIT_IDLE = 3, FIT_EXIT = 4 };      // beside TRF_PH_OUTER / INNER / DONE
-
-template <int BCAP> struct fit_waves { static constexpr int N = (BCAP <= 32) ? 2 : 1; };
-// lane groups of a wave that take fits: all eight while their LDS regions fit next to each other, six in the 256-row tier
-template <int BCAP> struct fit_groups { static constexpr int N = (BCAP <= 128) ? 8 : 6; };
 
 // Blocks of a kernel that serves the 16-row list (4-lane groups) and the 32-row list (8-lane groups): the first
 // fit_narrow_first_blocks() blocks start on the 16-row list, the others on the 32-row list, and every block goes on to
@@ -719,26 +713,29 @@ __device__ __forceinline__ void bazin_fit_loop(Region* R, const BatchView& B, co
 // list `tier` (bands of up to BCAP rows); the 32-row kernel also serves list 0 (up to 16 rows, 4-lane groups): a kernel
 // of its own behind the other four would add its longest fit to the end of the fit stream
 template <int BCAP>
-__global__ __launch_bounds__(64, (fit_waves<BCAP>::N)) void bazin_fit_kernel(BatchView B, Bins bins, FitWs F, int tier, SetOut O,
+__global__ __launch_bounds__(64, (fit_tier_row(BCAP).waves_bazin)) void bazin_fit_kernel(BatchView B, Bins bins, FitWs F, int tier, SetOut O,
                                                             unsigned long long* ticket, unsigned long long* ticket_narrow) {
-    constexpr int NG = fit_groups<BCAP>::N;
+    constexpr FitTierRow T = fit_tier_row(BCAP);
+    static_assert(T.id >= 0 && T.kernel, "a tier of fit_tier_table.hpp with kernels of its own");
+    constexpr int NG = T.groups;
     const int count = bins.counts[kFitCountBase + tier];
     const int* list = F.fits + (int64_t)tier * F.fit_stride;
-    if constexpr (BCAP == 32) {
-        __shared__ union Lds { FitRegion<32> wide[NG]; FitRegionNarrow narrow[16]; __device__ Lds() {} } R;
-        const int count_n = bins.counts[kFitCountBase];
+    if constexpr (T.id == kFitNarrowHost) {
+        __shared__ union Lds { FitRegion<BCAP> wide[NG]; FitRegionNarrow narrow[kFitNarrowGroups]; __device__ Lds() {} } R;
+        const int count_n = bins.counts[kFitCountBase + kFitNarrowTier];
+        const int* list_n = F.fits + (int64_t)kFitNarrowTier * F.fit_stride;
         const bool narrow_first = (int)blockIdx.x < fit_narrow_first_blocks(count_n, count);
         for (int pass = 0; pass < 2; ++pass) {
             if ((pass == 0) == narrow_first) {
-                if (count_n > 0) bazin_fit_loop<GroupDev<4>, 16>(R.narrow, B, F, F.fits, count_n, O, ticket_narrow);
+                if (count_n > 0) bazin_fit_loop<GroupDev<kFitNarrowLanes>, kFitNarrowGroups>(R.narrow, B, F, list_n, count_n, O, ticket_narrow);
             } else {
-                if (count > 0) bazin_fit_loop<GroupDev<8>, NG>(R.wide, B, F, list, count, O, ticket);
+                if (count > 0) bazin_fit_loop<GroupDev<T.lanes>, NG>(R.wide, B, F, list, count, O, ticket);
             }
             __syncthreads();
         }
     } else {
         __shared__ FitRegion<BCAP> R[NG];
-        bazin_fit_loop<GroupDev<8>, NG>(R, B, F, list, count, O, ticket);
+        bazin_fit_loop<GroupDev<T.lanes>, NG>(R, B, F, list, count, O, ticket);
     }
 }
 
@@ -809,9 +806,9 @@ __global__ __launch_bounds__(64, 2) void powerlaw_partition_kernel(BatchView B, 
                 if (threadIdx.x == 0) { F.kk[i * 3 + j] = k; F.peak[i * 3 + j] = peak_flux; F.sstot[i * 3 + j] = ss_tot; }
             }
             const int kmax = (kb[0] > kb[1]) ? ((kb[0] > kb[2]) ? kb[0] : kb[2]) : ((kb[1] > kb[2]) ? kb[1] : kb[2]);
-            if (kmax > kFitCaps[kFitTiers - 1]) {
+            if (kmax > kFitMaxRows) {
                 // more post-peak rows than the largest fit tier: object-level kernel (up to 1024 rows), else not available
-                if (n <= 1024) {
+                if (n <= kFitObjectRows) {
                     if (threadIdx.x == 0) bins.append(kPowerlawFallbackList, (int)i);
                 } else {
                     O.unavailable<W>(i, POWERLAW_NCOL, SetTraits<SET_POWERLAW>::nstatus);
@@ -907,28 +904,32 @@ __device__ __forceinline__ void powerlaw_fit_loop(Region* R, const BatchView& B,
 
 // list `tier` of the N-parameter models; the 32-row kernel also serves list 0 on 4-lane groups (see bazin_fit_kernel)
 template <int N, int BCAP>
-__global__ __launch_bounds__(64, (BCAP <= 64 ? 2 : 1)) void powerlaw_fit_kernel(BatchView B, Bins bins, PlWs F, int tier, SetOut O,
+__global__ __launch_bounds__(64, (fit_tier_row(BCAP).waves_decline)) void powerlaw_fit_kernel(BatchView B, Bins bins, PlWs F, int tier, SetOut O,
                                                                                   unsigned long long* ticket, unsigned long long* ticket_narrow) {
-    constexpr int NG = fit_groups<BCAP>::N;
+    constexpr FitTierRow T = fit_tier_row(BCAP);
+    static_assert(T.id >= 0 && T.kernel, "a tier of fit_tier_table.hpp with kernels of its own");
+    constexpr int NG = T.groups;
     constexpr int kCount = (N == 2) ? kPlCountA : kPlCountB;
     const int count = bins.counts[kCount + tier];
     const int* lists = (N == 2) ? F.fitsA : F.fitsB;
-    const int* list = lists + (int64_t)tier * ((N == 2) ? F.strideA : F.strideB);
-    if constexpr (BCAP == 32) {
-        __shared__ union Lds { PlRegion<N, 32> wide[NG]; PlRegion<N, 16> narrow[16]; __device__ Lds() {} } R;
-        const int count_n = bins.counts[kCount];
+    const int64_t stride = (N == 2) ? F.strideA : F.strideB;
+    const int* list = lists + (int64_t)tier * stride;
+    if constexpr (T.id == kFitNarrowHost) {
+        __shared__ union Lds { PlRegion<N, BCAP> wide[NG]; PlRegion<N, kFitNarrowRows> narrow[kFitNarrowGroups]; __device__ Lds() {} } R;
+        const int count_n = bins.counts[kCount + kFitNarrowTier];
+        const int* list_n = lists + (int64_t)kFitNarrowTier * stride;
         const bool narrow_first = (int)blockIdx.x < fit_narrow_first_blocks(count_n, count);
         for (int pass = 0; pass < 2; ++pass) {
             if ((pass == 0) == narrow_first) {
-                if (count_n > 0) powerlaw_fit_loop<GroupDev<4>, N, 16>(R.narrow, B, F, lists, count_n, O, ticket_narrow);
+                if (count_n > 0) powerlaw_fit_loop<GroupDev<kFitNarrowLanes>, N, kFitNarrowGroups>(R.narrow, B, F, list_n, count_n, O, ticket_narrow);
             } else {
-                if (count > 0) powerlaw_fit_loop<GroupDev<8>, N, NG>(R.wide, B, F, list, count, O, ticket);
+                if (count > 0) powerlaw_fit_loop<GroupDev<T.lanes>, N, NG>(R.wide, B, F, list, count, O, ticket);
             }
             __syncthreads();
         }
     } else {
         __shared__ PlRegion<N, BCAP> R[NG];
-        powerlaw_fit_loop<GroupDev<8>, N, NG>(R, B, F, list, count, O, ticket);
+        powerlaw_fit_loop<GroupDev<T.lanes>, N, NG>(R, B, F, list, count, O, ticket);
     }
 }
 
@@ -1317,82 +1318,79 @@ static int fit_waves_cap(int bcap) {
     return (e && atoi(e) > 0) ? atoi(e) : 0;
 }
 
-// Bazin: partition pass per object tier, the fit kernel per band-length tier (longest first), the object-level
-// kernel for objects with a band beyond the largest fit tier, then the cross-band columns.
-int SetLaunch::launch_bazin(const FitWs& F) const {
-    const int last = last_tier(max_len, 4);
-    unsigned long long* tk = tickets + SET_BAZIN * 8;
-    for (int ti = 0; ti <= last; ++ti) {
-        const int rc = for_tier(ti, [&](auto cap) {
-            return launch_grid(bazin_partition_kernel<cap()>, 64, {}, B.n_obj, 8, stream, dev, B, bins, ti, nan_from_of(ti, last), F, O, tk + ti,
-                               8, fit_narrow_enabled() ? 1 : 0);
-        });
-        if (rc) return rc;
-        ++*n_launch;
-    }
-    // objects with a band of more than 256 rows: the object-level kernel (all 52 columns).  A small grid, and AHEAD of the
-    // fit tiers: the list is normally empty, but every workgroup of this kernel needs 136 KiB of LDS -- at the end of the
-    // stream it sat in the dispatcher for 100-180 ms, until a GP tier released a whole CU (tools/step_timeline.py)
-    int rc = tier<SET_BAZIN, 1024>(kBazinFallbackList, kNumBins, stream, tk + 5, 32);
-    if (rc) return rc;
-    ++*n_launch;
-    // one ticket = 8 fits; (the 32-row launch serves the 16-row list as well: tier 0 has no kernel of its own)
-    unsigned long long* ftk = tickets + kFitTicketBase;
-    auto fits = [&](auto t) {
-        constexpr int T = t(), BCAP = kFitCaps[T];
-        return launch_grid(bazin_fit_kernel<BCAP>, 64, {fit_waves_cap(BCAP), 0}, kBazinFits * B.n_obj, 8, stream, dev, B, bins, F, T, O, ftk + T, ftk);
-    };
-    rc = fits(IntTag<4>{});
-    if (!rc) rc = fits(IntTag<3>{});
-    if (!rc) rc = fits(IntTag<2>{});
-    if (!rc) rc = fits(IntTag<1>{});
-    if (rc) return rc;
-    *n_launch += 4;
-    hipLaunchKernelGGL(bazin_cross_kernel, dim3((unsigned)((B.n_obj + 255) / 256)), dim3(256), 0, stream, B, O);
-    HIP_TRY(hipGetLastError());
-    ++*n_launch;
-    // the long-object tier: more than 2048 rows (bin 6), or more than 1024 rows with a band beyond the fit tiers (all 52 columns)
-    if (long_slabs && max_len > SetTraits<SET_BAZIN>::long_above) {
-        rc = long_tier<SET_BAZIN>(6, kBazinLongList, -1);
-        if (rc) return rc;
-        ++*n_launch;
-    }
-    return 0;
+// one fit kernel over list `tier` of the lists whose ticket counters start at tickets[ticket_base]; one ticket = 8 fits.
+// (The kernel of the narrow tier's host drains the narrow list as well and gets that list's counter too.)
+template <class K, class Ws>
+int SetLaunch::fit_stream(K kernel, int tier, int fits_per_object, int ticket_base, const Ws& F) const {
+    unsigned long long* tk = tickets + ticket_base;
+    const int rc = launch_grid(kernel, 64, {fit_waves_cap(fit_tier_cap(tier)), 0}, fits_per_object * B.n_obj, 8, stream, dev, B, bins, F, tier, O,
+                               tk + tier, tk + kFitNarrowTier);
+    if (!rc) ++*n_launch;
+    return rc;
 }
 
-int SetLaunch::launch_powerlaw(const PlWs& F) const {
+// The two fit-by-fit families as launch_fits takes them: the set, its share of the workspace, the partition kernel, the
+// fit kernels of one band-length tier, the lists of the light curves the fit tiers do not take, and what follows the fits.
+struct BazinFits {
+    using Ws = FitWs;
+    static constexpr int kSet = SET_BAZIN, kFallbackList = kBazinFallbackList, kLongList = kBazinLongList;
+    template <int CAP> static constexpr auto partition = bazin_partition_kernel<CAP>;
+    template <int T> static int fits(const SetLaunch& L, const Ws& F) {
+        return L.fit_stream(bazin_fit_kernel<fit_tier_cap(T)>, T, kBazinFits, kFitTicketBase, F);
+    }
+    // the cross-band columns, once all fits are in
+    static int epilogue(const SetLaunch& L) {
+        hipLaunchKernelGGL(bazin_cross_kernel, dim3((unsigned)((L.B.n_obj + 255) / 256)), dim3(256), 0, L.stream, L.B, L.O);
+        HIP_TRY(hipGetLastError());
+        ++*L.n_launch;
+        return 0;
+    }
+};
+struct DeclineFits {
+    using Ws = PlWs;
+    static constexpr int kSet = SET_POWERLAW, kFallbackList = kPowerlawFallbackList, kLongList = kPowerlawLongList;
+    template <int CAP> static constexpr auto partition = powerlaw_partition_kernel<CAP>;
+    // the two-parameter fits (list A), then the three-parameter ones (list B)
+    template <int T> static int fits(const SetLaunch& L, const Ws& F) {
+        if (const int rc = L.fit_stream(powerlaw_fit_kernel<2, fit_tier_cap(T)>, T, kPlFitsA, kPlTicketA, F)) return rc;
+        return L.fit_stream(powerlaw_fit_kernel<3, fit_tier_cap(T)>, T, kPlFitsB, kPlTicketB, F);
+    }
+    static int epilogue(const SetLaunch&) { return 0; }
+};
+
+// A fit-by-fit family: the partition pass per object tier, the object-level kernel for the light curves with a band beyond
+// the largest fit tier, the fit kernels per band-length tier (longest first), the family's epilogue, the long-object tier.
+template <class Fam>
+int SetLaunch::launch_fits(const typename Fam::Ws& F) const {
     const int last = last_tier(max_len, 4);
-    unsigned long long* tk = tickets + SET_POWERLAW * 8;
+    unsigned long long* tk = tickets + Fam::kSet * 8;
     for (int ti = 0; ti <= last; ++ti) {
         const int rc = for_tier(ti, [&](auto cap) {
-            return launch_grid(powerlaw_partition_kernel<cap()>, 64, {}, B.n_obj, 8, stream, dev, B, bins, ti, nan_from_of(ti, last), F, O, tk + ti,
+            return launch_grid(Fam::template partition<cap()>, 64, {}, B.n_obj, 8, stream, dev, B, bins, ti, nan_from_of(ti, last), F, O, tk + ti,
                                8, fit_narrow_enabled() ? 1 : 0);
         });
         if (rc) return rc;
         ++*n_launch;
     }
-    // the object-level kernel for the (normally empty) list of objects beyond the fit tiers, AHEAD of the fit tiers: see launch_bazin
-    int rc = tier<SET_POWERLAW, 1024>(kPowerlawFallbackList, kNumBins, stream, tk + 5, 32);
+    // light curves with a band of more rows than the largest fit tier: the object-level kernel (all columns).  A small grid,
+    // and AHEAD of the fit tiers: the list is normally empty, but every workgroup of this kernel needs 136 KiB of LDS -- at the
+    // end of the stream it sat in the dispatcher for 100-180 ms, until a GP tier released a whole CU (tools/step_timeline.py)
+    int rc = tier<Fam::kSet, kFitObjectRows>(Fam::kFallbackList, kNumBins, stream, tk + 5, 32);
     if (rc) return rc;
     ++*n_launch;
-    // per band-length tier the two-parameter fits (list A), then the three-parameter ones (list B); one ticket = 8 fits
-    // (the 32-row launches serve the 16-row lists as well: tier 0 has no kernels of its own)
-    auto fits = [&](auto t) {
-        constexpr int T = t(), BCAP = kFitCaps[T];
-        const int ra = launch_grid(powerlaw_fit_kernel<2, BCAP>, 64, {fit_waves_cap(BCAP), 0}, kPlFitsA * B.n_obj, 8, stream, dev, B, bins, F, T,
-                                   O, tickets + kPlTicketA + T, tickets + kPlTicketA);
-        if (ra) return ra;
-        return launch_grid(powerlaw_fit_kernel<3, BCAP>, 64, {fit_waves_cap(BCAP), 0}, kPlFitsB * B.n_obj, 8, stream, dev, B, bins, F, T, O,
-                           tickets + kPlTicketB + T, tickets + kPlTicketB);
-    };
-    rc = fits(IntTag<4>{});
-    if (!rc) rc = fits(IntTag<3>{});
-    if (!rc) rc = fits(IntTag<2>{});
-    if (!rc) rc = fits(IntTag<1>{});
+    // the tiers of fit_tier_table.hpp that have kernels of their own, longest first
+    for (int t = kFitTiers - 1; t >= 0 && !rc; --t)
+        switch (t) {
+#define X(id, BCAP, LANES, GROUPS, WB, WD, KERNEL) case id: if constexpr (KERNEL) rc = Fam::template fits<id>(*this, F); break;
+            LCFE_FIT_TIERS(X)
+#undef X
+        }
+    if (!rc) rc = Fam::epilogue(*this);
     if (rc) return rc;
-    *n_launch += 8;
-    if (long_slabs && max_len > SetTraits<SET_POWERLAW>::long_above) {
-        rc = long_tier<SET_POWERLAW>(6, kPowerlawLongList, -1);
+    // the long-object tier: more rows than the LDS tiers take (bin 6), or than the object-level kernel takes with a band
+    // beyond the fit tiers (all columns)
+    if (long_slabs && max_len > SetTraits<Fam::kSet>::long_above) {
+        rc = long_tier<Fam::kSet>(6, Fam::kLongList, -1);
         if (rc) return rc;
         ++*n_launch;
     }
@@ -1913,8 +1911,8 @@ int lcfe_extract_device(int mask, int device, void* stream_, int64_t n_obj, int6
         const int rc = for_set(s, [&](auto tag) -> int {
             constexpr int SET = tag();
             if constexpr (SET == SET_STAT) return A.launch_stat(fork ? side[0] : q, fork ? side[1] : q);
-            else if constexpr (SET == SET_BAZIN) return A.launch_bazin(bazin_ws(L, d_workspace));
-            else if constexpr (SET == SET_POWERLAW) return A.launch_powerlaw(powerlaw_ws(L, d_workspace));
+            else if constexpr (SET == SET_BAZIN) return A.launch_fits<BazinFits>(bazin_ws(L, d_workspace));
+            else if constexpr (SET == SET_POWERLAW) return A.launch_fits<DeclineFits>(powerlaw_ws(L, d_workspace));
             else if constexpr (SET == SET_GP1D) return A.launch_gp1d((double*)L.at(d_workspace, WS_GP1D));
             else if constexpr (SET == SET_GP2D) {
                 // the GP tiers, longest first, round-robin over the caller's stream and side streams 2.. (LCFE_GP_STREAMS, default

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "feature_sets.hpp"
+#include "fit_tier_table.hpp"
 #include "gp_tier_table.hpp"
 
 namespace lcfe {
@@ -38,7 +39,7 @@ static_assert(SetTraits<SET_GP2D>::long_above == kGpLastCap && SetTraits<SET_GP1
 // lists' lengths, then the fit lists'), [2048, 2304) ticket counters of the registered sets (8 per set)
 constexpr size_t kWsHeader = 2304;
 constexpr size_t kWsCounts = 1024;                          // byte offset of counts[]
-constexpr int kFitTiers = 5;                                // band-length tiers of the fit lists (lcfe.hip: kFitCaps)
+// (kFitTiers band-length tiers of the fit lists: fit_tier_table.hpp)
 constexpr int kFitCountBase = 32;                           // counts[32 + t]: length of fit list t
 constexpr int kPlCountA = 40, kPlCountB = 48;               // counts[40 + t], counts[48 + t]
 // (the ticket counters of the fit lists sit behind those of the numbered sets and the extension set: 8 per set, 13 sets;
@@ -50,6 +51,10 @@ static_assert(kFitTicketBase >= (SET_ADVANCED + 1) * 8, "fit tickets behind the 
 static_assert(kFitCountBase >= kNumLists && kFitCountBase + kFitTiers <= kPlCountA && kPlCountA + kFitTiers <= kPlCountB && kPlCountB + kFitTiers <= 256,
               "count slots of the fit lists");
 static_assert(kPlTicketB + kFitTiers <= 128, "ticket slots of the fit lists");
+// a light curve with a band beyond the fit tiers goes to the set's object-level kernel while that kernel's largest LDS tier
+// takes it (the set table's), and to the long-object tier beyond
+constexpr int kFitObjectRows = kTiers[SetTraits<SET_BAZIN>::max_tier];
+static_assert(kTiers[SetTraits<SET_POWERLAW>::max_tier] == kFitObjectRows, "one object-level cap for the Bazin and the decline fits");
 static_assert(SetTraits<SET_CESIUM>::ticket_base == kRegTicketBase && NUM_ALL_SETS - SET_CESIUM <= kRegTicketSets,
               "ticket counters of the registered sets");
 static_assert((SET_ADVANCED + 1) * 8 <= kFitTicketBase && kPlTicketB + kFitTiers <= 128, "ticket counters of the first 1024 bytes");

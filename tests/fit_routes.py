@@ -18,7 +18,10 @@ FIXTURE = os.path.join(HERE, "golden", "golden_fit_routes.npz")
 
 GROUPS = ("T16", "T32", "T64", "T128", "T256", "OBJ", "LONG", "MIX", "FAIL", "K256")
 PROBES = ("_p1", "_p2", "_m1", "_m2", "_m3")
-FIT_CAPS = (16, 32, 64, 128, 256)                      # kFitCaps of lcfe.hip: rows of one band per fit-by-fit list
+# rows of one band per fit-by-fit list, and the rows of the object-level kernels behind them: restatements of
+# csrc/fit_tier_table.hpp and kFitObjectRows of csrc/workspace.hpp (held against them by tests/test_fit_tier_table_cpu.py)
+FIT_CAPS = (16, 32, 64, 128, 256)
+OBJECT_ROWS = 1024
 # routes of one fit
 LIST0, LIST1, LIST2, LIST3, LIST4, R_OBJ, R_LONG, R_NONE = range(8)
 ROUTE_NAMES = ("list0", "list1", "list2", "list3", "list4", "object", "long", "none")
@@ -104,7 +107,7 @@ def fit_routes(csr):
     bz = _list_of(rows)
     bz[rows < 5] = R_NONE
     whole = (rows.max(1) > FIT_CAPS[-1]) | (n > 2048)
-    obj = whole & (n <= 1024)
+    obj = whole & (n <= OBJECT_ROWS)
     bz[obj[:, None] & (rows >= 5)] = R_OBJ
     bz[(whole & ~obj)[:, None] & (rows >= 5)] = R_LONG
     # decline fits: nine per band g, r, i with >= 5 rows and >= 3 post-peak rows, routed by the post-peak count
@@ -114,7 +117,7 @@ def fit_routes(csr):
     pl[~fitted] = R_NONE
     kmax = np.where(fitted, k, 0).max(1)
     whole = (kmax > FIT_CAPS[-1]) | (n > 2048)
-    obj = whole & (n <= 1024)
+    obj = whole & (n <= OBJECT_ROWS)
     pl[obj[:, None] & fitted] = R_OBJ
     pl[(whole & ~obj)[:, None] & fitted] = R_LONG
     return bz, np.repeat(pl, 9, axis=1), rows, post

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "run_all.hpp"
+#include "../../mallorn-astrophysics_amd/csrc/workspace.hpp"
 
 using namespace lcfe;
 
@@ -80,6 +81,20 @@ extern "C" int hostsim_gp_tier_info(int ti, int* o) {
     for (int k = 0; k < 8; ++k) o[k] = v[k];
     return 0;
 }
+
+// the band-length tiers of the fit-by-fit kernels (csrc/fit_tier_table.hpp) and the object-level cap behind them
+// (csrc/workspace.hpp), for the tests' own restatements (tests/test_fit_tier_table_cpu.py)
+extern "C" int hostsim_fit_tiers() { return kFitTiers; }
+// o[5]: rows of one band, lanes per fit, lane groups per wave, has kernels of its own, the tier whose kernels run its list
+extern "C" int hostsim_fit_tier_info(int t, int* o) {
+    if (t < 0 || t >= kFitTiers) return 1;
+    const FitTierRow& r = kFitTierTable[t];
+    const int v[5] = {fit_tier_cap(t), r.lanes, r.groups, r.kernel, fit_tier_host(t)};
+    for (int k = 0; k < 5; ++k) o[k] = v[k];
+    return 0;
+}
+extern "C" int hostsim_fit_tier_of(int m, int narrow) { return fit_tier_of(m, narrow); }
+extern "C" int hostsim_fit_object_rows() { return kFitObjectRows; }
 
 extern "C" int hostsim_extract(int set, int64_t n_obj, const int64_t* offsets, const double* t,
                                const double* flux, const double* err, const uint8_t* band,

@@ -22,6 +22,7 @@ N_OBJ = 384
 SEED = 20261016
 BAND_ROWS = (0, 4, 5, 15, 16, 17, 32, 9, 12, 33, 70)          # rows of one band, drawn per (object, band)
 POST_ROWS = (2, 3, 15, 16, 17, 32, 5, 8)                      # wanted rows after the peak of a band (capped by its length)
+NARROW_ROWS, WIDE_ROWS = 16, 32                               # caps of the two lists (csrc/fit_tier_table.hpp: tiers 0 and 1)
 
 
 def make_batch():
@@ -70,12 +71,12 @@ def make_batch():
 
 def list_counts(rows, post):
     """Fits per side of the tier edge, as the partition kernels count them."""
-    bz_narrow = int(((rows >= 5) & (rows <= 16)).sum())
-    bz_wide = int(((rows >= 17) & (rows <= 32)).sum())
+    bz_narrow = int(((rows >= 5) & (rows <= NARROW_ROWS)).sum())
+    bz_wide = int(((rows > NARROW_ROWS) & (rows <= WIDE_ROWS)).sum())
     gri = slice(1, 4)
     fitted = (rows[:, gri] >= 5) & (post[:, gri] >= 3)
-    pl_narrow = int((fitted & (post[:, gri] <= 16)).sum())
-    pl_wide = int((fitted & (post[:, gri] >= 17) & (post[:, gri] <= 32)).sum())
+    pl_narrow = int((fitted & (post[:, gri] <= NARROW_ROWS)).sum())
+    pl_wide = int((fitted & (post[:, gri] > NARROW_ROWS) & (post[:, gri] <= WIDE_ROWS)).sum())
     return bz_narrow, bz_wide, pl_narrow, pl_wide
 
 
