@@ -17,6 +17,8 @@
 //     `maxiter` iterations (scipy's driver loop).
 // The state machine is reverse-communication like the original: the caller evaluates f and g.
 // Everything here is wave/block-uniform scalar code (n = 4 parameters).
+// tests/test_lbfgsb_cpu.py drives the host build with the same Python objective as scipy and replays recorded scipy runs
+// step by step; tests/test_gpu_lbfgsb.py replays them through both device instantiations of lb_advance.
 #pragma once
 #include <type_traits>
 #include "wave.hpp"

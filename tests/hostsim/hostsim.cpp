@@ -187,3 +187,40 @@ extern "C" int hostsim_lbfgsb_box3(double* x, const double* lo, const double* hi
     *f_out = f;
     return rc;
 }
+
+// ---- unbounded L-BFGS-B (csrc/lbfgsb.hpp), the 2-D GP's driver, by itself (tests/test_lbfgsb_cpu.py): the product's
+// constants -- factr 1e7, pgtol 1e-5, maxls 20 (gp_object's lb_start) -- and M = 10 pairs over 4 variables.
+// Closed loop: lbfgsb_minimize on the caller's objective, the same Python function the test hands to scipy.
+extern "C" int hostsim_lbfgsb4(double* x, hostsim_fg_t fg, int maxiter, double* f_out, int* n_iter, int* n_eval) {
+    auto S = std::make_unique<LbState<4, 10>>();
+    double xx[4] = {x[0], x[1], x[2], x[3]}, f = 0;
+    auto ev = [&](const double* p, double& fv, double* gv) { fg(p, &fv, gv); };
+    const int why = lbfgsb_minimize<4, 10>(xx, f, ev, maxiter, 1e7, 1e-5, 20, *n_iter, *n_eval, *S);
+    for (int i = 0; i < 4; ++i) x[i] = xx[i];
+    *f_out = f;
+    return why;
+}
+
+// Replay of a recorded run (tests/lb_reference.py): lb_start, then for k < ne the taped f[k], g[k][4] are stored and
+// lb_advance<4, 10> is called; stops at the first result other than LB_EVAL or at the end of the tape.  x_out: [ne + 1][4],
+// the requested point after every step (row 0 = x0); why, n_iter, n_eval: [ne] per step; x_final[4], f_final.  Returns the
+// number of steps taken.  The device counterpart is tests/devprobe/lb_probe.hip.
+extern "C" int hostsim_lb_replay(const double* x0, int maxiter, int ne, const double* tape_f, const double* tape_g,
+                                 double* x_out, int* why, int* n_iter, int* n_eval, double* x_final, double* f_final) {
+    auto S = std::make_unique<LbState<4, 10>>();
+    lb_start(*S, x0, maxiter, 1e7, 1e-5, 20);
+    for (int i = 0; i < 4; ++i) x_out[i] = S->x[i];
+    int k = 0;
+    while (k < ne) {
+        S->f = tape_f[k];
+        for (int i = 0; i < 4; ++i) S->g[i] = tape_g[4 * k + i];
+        const int w = lb_advance<4, 10>(*S);
+        why[k] = w; n_iter[k] = S->n_iter; n_eval[k] = S->n_eval;
+        ++k;
+        for (int i = 0; i < 4; ++i) x_out[4 * k + i] = S->x[i];
+        if (w != LB_EVAL) break;
+    }
+    for (int i = 0; i < 4; ++i) x_final[i] = S->x[i];
+    *f_final = S->f;
+    return k;
+}

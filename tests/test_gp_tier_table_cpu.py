@@ -11,6 +11,7 @@ import re
 
 import numpy as np
 
+import gp2d_driver_inputs as drv
 import gp2d_tier_pin_inputs as pin
 import gp_eval_reference as ref
 import gp_sweep_tiles as tiles
@@ -30,6 +31,7 @@ def exported():
 
 
 def test_python_tables_restate_the_tier_table():
+    L = hostsim_lib.lib()
     rows = exported()
     nps = [r[0] for r in rows]
     # a tier's cap is NP - 1, its first count the cap before it + 1 (tier 0: gp_object's 10 points)
@@ -58,3 +60,10 @@ def test_python_tables_restate_the_tier_table():
         assert (lo, hi) == (first, cap) and lo < mid < hi, np_
     quoted = re.search(r"\((\d+(?:, \d+)+);", pin.__doc__)
     assert quoted and [int(v) for v in quoted.group(1).split(",")] == [r[2] for r in rows]
+
+    # gp2d_driver_inputs: one tier object per tier and one for the long-object tier, and the caps it restates
+    caps = [r[2] for r in rows]
+    assert list(drv.TIER_CAPS) == caps
+    assert [drv.tier_of(n) for n in drv.TIER_COUNTS] == list(range(len(rows) + 1))
+    assert all(L.hostsim_gp_tier_info(ctypes.c_int(drv.tier_of(n)), np.zeros(8, np.int32).ctypes.data_as(ctypes.POINTER(ctypes.c_int))) == 0
+               for n in drv.TIER_COUNTS[:-1]) and drv.TIER_COUNTS[-1] > caps[-1]

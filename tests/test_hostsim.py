@@ -53,6 +53,12 @@ def test_hostsim_gp2d_vs_oracle(golden_inputs):
     got[rows] = o
     mask = np.zeros(len(ref), bool); mask[rows] = True
     check_fit_parity(got[mask], "gp2d", COLUMNS["gp2d"], ref=ref[mask], probes=[p[mask] for p in probes])
+    # the driver's status words against scipy's own counts on these rows (tests/gp2d_driver_inputs.py: the rules of
+    # tests/test_gpu_gp2d_driver.py)
+    import gp2d_driver_inputs as drv
+    fx = drv.load()
+    share = drv.check_status(st, {k: v[rows] for k, v in fx.items()}, drv.held_out_share(fx), "host")
+    print("host share on stable objects:", share)
 
 
 def test_gp1d_templates_match_reference_golden(golden_inputs):
