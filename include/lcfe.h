@@ -219,6 +219,33 @@ int lcfe_augment_device(int device, void* stream, int64_t n_obj, int64_t n_point
                         void* d_workspace, size_t workspace_bytes);
 
 /*
+ * The augmentation recipes of gp_augmentation.py (Boone: time shift, sparsening, S/N degradation) and of
+ * plasticc_augmentation.py (redshift dilation and dimming, per-band skew, quality degradation): lcfe_augment_device with five
+ * more arguments.  Per kept row, in this order (multiplies and adds are never fused):
+ *   1. flux *= scale, err *= scale                       2. the stretch             3. flux += err * noise_scale * N(0, 1)
+ *      (stream 0), then flux += add_flux
+ *   4. band b < 6: flux *= band_scale[b], err *= band_scale[b]; a row of filter 255 is left as it is
+ *   5. the dropout selection (stream 1), keeping per keep_rule
+ *        0  max(5, (int64)(n * (1 - dropout))) rows, objects of up to 5 rows whole -- the rule of lcfe_augment_device
+ *        1  n - (int64)(n * dropout) rows, no floor (gp_augmentation.py:60-61)
+ *   6. err *= err_boost                                  7. flux += err * noise2_scale * N(0, 1) with the boosted err, drawn
+ *      from stream 3 -- counter (row index in the input object, 3, 0, 0), the same Box-Muller --, then flux += add_flux2
+ *   8. the shift                                         9. the band noise
+ *   band_scale    float64[n_obj * k, 6] (u g r i z y), err_boost and noise2_scale float64[n_obj * k]; NULL = neutral (1, 1, 0)
+ *   add_flux2     optional, per candidate row like add_flux
+ * With the three arrays and add_flux2 NULL (or neutral) and keep_rule 0 the output is that of lcfe_augment_device, byte for
+ * byte.  Capacity, workspace and outputs as there; errors as there, plus a keep_rule other than 0 and 1.
+ */
+int lcfe_augment_recipe_device(int device, void* stream, int64_t n_obj, int64_t n_points, int k, const int64_t* d_offsets,
+                               const double* d_t, const double* d_flux, const double* d_err, const uint8_t* d_band,
+                               const double* d_scale, const double* d_stretch, const double* d_shift, const double* d_noise_scale,
+                               const double* d_dropout, const uint8_t* d_band_noise, const uint64_t* d_seed,
+                               const double* d_band_scale, const double* d_err_boost, const double* d_noise2_scale, int keep_rule,
+                               const double* d_add_flux, const uint8_t* d_keep, const double* d_add_flux2, int64_t* d_offsets_out,
+                               double* d_t_out, double* d_flux_out, double* d_err_out, uint8_t* d_band_out, int64_t* d_n_points_out,
+                               void* d_workspace, size_t workspace_bytes);
+
+/*
  * Sequence tensors on the device (models/lightcurve_dataset.py:79-127, 141-170, LightcurveDataset): a device-resident CSR
  * batch -- a staged one or the output of lcfe_augment_device -- to the padded float32 inputs of the sequence classifiers.
  * No feature set: no mask bit, no columns.  Like lcfe_extract_device: every pointer is a DEVICE pointer on `device`, the

@@ -111,6 +111,10 @@ def load():
     lib.lcfe_augment_device.restype = ctypes.c_int
     lib.lcfe_augment_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + \
                                        [ctypes.c_void_p] * 21 + [ctypes.c_size_t]
+    # batch (5) + plan (7) + band_scale, err_boost, noise2_scale; keep_rule; add_flux, keep, add_flux2 + outputs (6) + workspace
+    lib.lcfe_augment_recipe_device.restype = ctypes.c_int
+    lib.lcfe_augment_recipe_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + \
+                                              [ctypes.c_void_p] * 15 + [ctypes.c_int] + [ctypes.c_void_p] * 10 + [ctypes.c_size_t]
     lib.lcfe_sequences_workspace_bytes.restype = ctypes.c_size_t
     lib.lcfe_sequences_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
     lib.lcfe_sequences_device.restype = ctypes.c_int

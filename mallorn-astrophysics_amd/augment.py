@@ -5,6 +5,13 @@ one object at a time, before any feature is extracted.  Here the batch is packed
 (``engine.DeviceBatch``), ``DeviceBatch.augment(plan)`` writes the copies in HBM (``lcfe_augment_device``) and the result is
 an ordinary batch for ``run()``: the K-fold rows never cross PCIe.  DESIGN.md "Augmentation" has the step order, the
 generator and the differences from the reference.
+
+The augmented trainings start from two other recipes: Boone's (``src/features/gp_augmentation.py``:
+``create_augmented_dataset`` -- time shift, random sparsening, S/N degradation or all three) and the PLAsTiCC one
+(``src/features/plasticc_augmentation.py``: ``augment_for_test_distribution`` -- redshift dilation and dimming, a per-band
+skew, sometimes a quality degradation).  ``RecipePlan`` holds what they need beyond an ``AugmentPlan``,
+``DeviceBatch.augment_recipe(plan)`` runs it (``lcfe_augment_recipe_device``), ``boone_augment_and_extract`` and
+``plasticc_augment_and_extract`` are the entry points.  DESIGN.md "The Boone and PLAsTiCC recipes on the device".
 """
 from __future__ import annotations
 
@@ -16,6 +23,11 @@ _DTYPES = {"scale": np.float64, "stretch": np.float64, "shift": np.float64, "noi
 # probabilities with which augment_single applies a step (augmentation.py:156-182; the flux scale always) and its shift range
 P_STRETCH, P_NOISE, P_DROPOUT, P_SHIFT, P_BAND = 0.8, 0.7, 0.5, 0.3, 0.4
 SHIFT_RANGE = (-100.0, 100.0)
+RECIPE_FIELDS = ("band_scale", "err_boost", "noise2_scale")
+KEEP_FLOOR5, KEEP_BOONE = 0, 1          # rows kept of n: max(5, int(n (1 - d))) (objects of up to 5 rows whole); n - int(n d)
+BOONE_STRATEGIES = ("time_shift", "sparse", "noise", "combined")
+# flat LambdaCDM of plasticc_augmentation.py:30-33
+H0, OMEGA_M, OMEGA_L, C_KMS = 70.0, 0.3, 0.7, 299792.458
 
 
 class AugmentPlan:
@@ -71,6 +83,220 @@ class AugmentPlan:
         seed = (rng.randint(0, 2 ** 32, m, dtype=np.uint64) << np.uint64(32)) | rng.randint(0, 2 ** 32, m, dtype=np.uint64)
         return cls(n_obj, n_copies, scale=scale, stretch=stretch, shift=shift, noise_scale=noise, dropout=dropout,
                    band_noise=band, seed=seed)
+
+
+def luminosity_distance(z):
+    """d_L in Mpc as ``plasticc_augmentation.luminosity_distance`` computes it (lines 36-60), for an array of redshifts: the
+    100-term sum ``(c / H0) sum(1 / E(z_j)) (z / 100)`` over ``z_j = linspace(0, z, 100)``, times ``1 + z``; 0 for z <= 0."""
+    z = np.asarray(z, np.float64)
+    flat = np.atleast_1d(z).ravel()
+    out = np.zeros(flat.size)
+    for lo in range(0, flat.size, 65536):
+        zz = flat[lo:lo + 65536]
+        z_arr = np.ascontiguousarray(np.linspace(0, zz, 100, axis=-1))
+        e_z = np.sqrt(OMEGA_M * (1 + z_arr) ** 3 + OMEGA_L)
+        d_c = (C_KMS / H0) * np.sum(1.0 / e_z, axis=-1) * (zz / 100)
+        out[lo:lo + 65536] = np.where(zz > 0, (1 + zz) * d_c, 0.0)
+    return out.reshape(z.shape)
+
+
+def _seeds(rng, m):
+    return (rng.randint(0, 2 ** 32, m, dtype=np.uint64) << np.uint64(32)) | rng.randint(0, 2 ** 32, m, dtype=np.uint64)
+
+
+class RecipePlan(AugmentPlan):
+    """An ``AugmentPlan`` with the steps of the Boone and PLAsTiCC recipes: ``band_scale`` [n_obj * n_copies, 6] (u g r i z y)
+    multiplies the flux and the error of a band after the noise step, ``err_boost`` multiplies the error after the dropout,
+    ``noise2_scale`` adds a second noise term in units of the boosted error; neutral 1, 1, 0 (the default).  ``keep_rule``:
+    how many of an object's n rows a dropout d keeps -- ``KEEP_FLOOR5`` as in ``AugmentPlan``, ``KEEP_BOONE`` ``n - int(n d)``.
+    ``z_out``: optional, the redshift of every copy."""
+
+    def __init__(self, n_obj, n_copies, band_scale=None, err_boost=None, noise2_scale=None, keep_rule=KEEP_FLOOR5, z_out=None,
+                 **arrays):
+        super().__init__(n_obj, n_copies, **arrays)
+        m = self.n_obj * self.n_copies
+        given = {"band_scale": band_scale, "err_boost": err_boost, "noise2_scale": noise2_scale, "z_out": z_out}
+        neutral = {"band_scale": lambda: np.ones((m, 6)), "err_boost": lambda: np.ones(m), "noise2_scale": lambda: np.zeros(m)}
+        for name, a in given.items():
+            if a is None:
+                a = neutral[name]() if name in neutral else None
+            else:
+                a = np.ascontiguousarray(a, np.float64)
+                if a.shape != ((m, 6) if name == "band_scale" else (m,)):
+                    raise ValueError(f"{name} must have n_obj * n_copies = {m} entries" + (" of 6 bands" if name == "band_scale" else ""))
+            setattr(self, name, a)
+        if not (np.isfinite(self.band_scale).all() and np.isfinite(self.err_boost).all()):
+            raise ValueError("band_scale and err_boost must be finite")
+        if keep_rule not in (KEEP_FLOOR5, KEEP_BOONE):
+            raise ValueError("keep_rule must be KEEP_FLOOR5 (0) or KEEP_BOONE (1)")
+        self.keep_rule = int(keep_rule)
+
+    def recipe_arrays(self):
+        return {name: getattr(self, name) for name in RECIPE_FIELDS}
+
+    def with_identity_copy(self):
+        """The plan with an identity copy in front of each object's copies (its redshift NaN where the plan has ``z_out``:
+        the caller fills in the object's own)."""
+        k = self.n_copies
+        ident = RecipePlan.identity(self.n_obj, 1)
+        fields = {**self.arrays(), **self.recipe_arrays()}
+        first = {**ident.arrays(), **ident.recipe_arrays()}
+        merged = {name: np.concatenate([first[name].reshape(self.n_obj, 1, -1), a.reshape(self.n_obj, k, -1)], axis=1)
+                  .reshape((-1, 6) if name == "band_scale" else -1) for name, a in fields.items()}
+        z_out = None if self.z_out is None else np.concatenate([np.full((self.n_obj, 1), np.nan), self.z_out.reshape(-1, k)], axis=1).ravel()
+        return RecipePlan(self.n_obj, k + 1, keep_rule=self.keep_rule, z_out=z_out, **merged)
+
+    @classmethod
+    def boone(cls, n_obj, n_copies, random_seed=42):
+        """-> (plan, strategy name per copy).  Per copy one of the four strategies of ``create_augmented_dataset``
+        (gp_augmentation.py:198-217) with equal probability and its ranges: ``time_shift`` +-20 days; ``sparse`` a drop
+        fraction in 0.1-0.3; ``noise`` a factor f in 1.2-2.0; ``combined`` +-10 days, 0.1-0.2 and 1.1-1.5.  The factor f
+        becomes ``noise_scale = f - 1`` and ``err_boost = f`` (gp_augmentation.py:88-92); ``keep_rule`` is Boone's.
+
+        The distributions are the reference's, the values are not: its functions reseed numpy's global generator in the
+        middle of the loop that draws the strategies."""
+        rng = np.random.RandomState(random_seed)
+        m = int(n_obj) * int(n_copies)
+        strat = rng.randint(0, 4, m)
+        u = rng.random_sample((3, m))
+        both = strat == 3
+        shift = np.where(strat == 0, -20.0 + 40.0 * u[0], np.where(both, -10.0 + 20.0 * u[0], 0.0))
+        drop = np.where(strat == 1, 0.1 + 0.2 * u[1], np.where(both, 0.1 + 0.1 * u[1], 0.0))
+        factor = np.where(strat == 2, 1.2 + 0.8 * u[2], np.where(both, 1.1 + 0.4 * u[2], 1.0))
+        plan = cls(n_obj, n_copies, scale=np.ones(m), stretch=np.ones(m), shift=shift, noise_scale=factor - 1.0, dropout=drop,
+                   band_noise=np.zeros(m, np.uint8), seed=_seeds(rng, m), err_boost=factor, keep_rule=KEEP_BOONE)
+        return plan, [BOONE_STRATEGIES[j] for j in strat]
+
+    @classmethod
+    def plasticc(cls, z_orig, n_copies, target_z=None, z_range=(0.1, 1.5), skew_range=(-0.2, 0.2), degrade_prob=0.5, random_state=42):
+        """The plan of ``PLAsTiCCAugmenter.augment_single`` for objects at the redshifts ``z_orig``: per copy a new redshift
+        -- drawn from ``target_z`` when given, else uniform in ``z_range`` --, ``stretch = (1 + z_new) / (1 + z_orig)``,
+        ``scale = ((d_L(z_orig) + 1e-10) / (d_L(z_new) + 1e-10))^2``, ``noise_scale = 1 / sqrt(scale) - 1`` where ``z_new >
+        z_orig`` and ``sqrt(scale) < 1`` (plasticc_augmentation.py:93-115), ``band_scale = 1 + delta_b`` with ``delta_b``
+        uniform in ``skew_range`` (lines 143-147) and, with probability ``degrade_prob``, a dropout in 0.1-0.3 and an error
+        boost in 1.2-2.0 with ``noise2_scale = (boost - 1) / boost`` (lines 254-257, 178-185).  ``z_out`` is ``z_new``."""
+        rng = np.random.RandomState(random_state)
+        z_orig = np.ascontiguousarray(z_orig, np.float64)
+        if z_orig.ndim != 1 or not np.isfinite(z_orig).all():
+            raise ValueError("z_orig must be one finite redshift per object")
+        k = int(n_copies)
+        m = z_orig.size * k
+        z_new = rng.choice(np.asarray(target_z, np.float64), m) if target_z is not None else rng.uniform(z_range[0], z_range[1], m)
+        zo = np.repeat(z_orig, k)
+        scale = ((luminosity_distance(zo) + 1e-10) / (luminosity_distance(z_new) + 1e-10)) ** 2
+        sn = np.sqrt(scale)
+        with np.errstate(divide="ignore"):
+            noise = np.where((z_new > zo) & (sn < 1), 1 / sn - 1, 0.0)
+        band_scale = 1 + rng.uniform(skew_range[0], skew_range[1], (m, 6))
+        degrade = rng.random_sample(m) < degrade_prob
+        dropout = np.where(degrade, rng.uniform(0.1, 0.3, m), 0.0)
+        boost = np.where(degrade, rng.uniform(1.2, 2.0, m), 1.0)
+        return cls(z_orig.size, k, scale=scale, stretch=(1 + z_new) / (1 + zo), shift=np.zeros(m), noise_scale=noise, dropout=dropout,
+                   band_noise=np.zeros(m, np.uint8), seed=_seeds(rng, m), band_scale=band_scale, err_boost=boost,
+                   noise2_scale=(boost - 1) / boost, keep_rule=KEEP_FLOOR5, z_out=z_new)
+
+
+def boone_ids(kept_ids, positions, plan, strategies, random_seed=42):
+    """Ids of the copies as ``augment_single_object`` names them (gp_augmentation.py:117, 122, 127, 142): ``_shift{int(d):+d}``,
+    ``_sparse{int(100 frac)}``, ``_noise{int(10 f)}`` and, for ``combined``, ``_aug{random_seed + i k + c}`` with ``i`` =
+    ``positions[j]``, the object's index in the metadata."""
+    k, ids = plan.n_copies, []
+    for j, oid in enumerate(kept_ids):
+        for c in range(k):
+            o = j * k + c
+            s = strategies[o]
+            if s == "time_shift":
+                ids.append(f"{oid}_shift{int(plan.shift[o]):+d}")
+            elif s == "sparse":
+                ids.append(f"{oid}_sparse{int(plan.dropout[o] * 100)}")
+            elif s == "noise":
+                ids.append(f"{oid}_noise{int(plan.err_boost[o] * 10)}")
+            else:
+                ids.append(f"{oid}_aug{random_seed + positions[j] * k + c}")
+    return ids
+
+
+def _run_recipe(csr, z, plan, mask, with_originals):
+    """One staged batch, one recipe call, one engine call -> (rows of the originals or None, rows of the copies)."""
+    from .engine import DeviceBatch
+
+    n, k = plan.n_obj, plan.n_copies
+    if with_originals:                  # the originals ride along as an identity copy in front of each object's copies
+        plan = plan.with_identity_copy()
+        if plan.z_out is not None:
+            zz = plan.z_out.reshape(n, k + 1)
+            zz[:, 0] = np.nan if z is None else z
+    out = DeviceBatch(csr, z=z).augment_recipe(plan).run(mask)[0].cpu().numpy().reshape(n, plan.n_copies, -1)
+    if with_originals:
+        return out[:, 0], out[:, 1:].reshape(n * k, -1)
+    return None, out.reshape(n * k, -1)
+
+
+def boone_augment_and_extract(lightcurves, metadata, sets, n_augmentations_per_object=3, random_seed=42):
+    """``create_augmented_dataset`` (gp_augmentation.py:154-251) followed by the extraction of ``sets``, on the device: pack
+    once, one ``augment_recipe``, one engine call -> ``(frame, meta)``.  ``frame``: ``object_id`` first, then the columns of
+    the sets in mask-bit order; the originals first, then per object its copies.  ``meta``: ``object_id, target, original_id,
+    augmentation_type`` -- ``'original'`` for the originals, the strategy for a copy -- row for row with ``frame``.  Objects
+    of the metadata without rows are left out, of the originals too: there is nothing to extract from."""
+    import pandas as pd
+
+    from .engine import columns_of, mask_of, sets_of
+    from .features._frame import NEEDS_Z, redshifts
+    from .packing import pack_lightcurves
+
+    mask = mask_of(sets)
+    k = int(n_augmentations_per_object)
+    object_ids = metadata["object_id"].tolist()
+    csr, kept = pack_lightcurves(lightcurves, object_ids)
+    where = {}
+    for j, oid in enumerate(object_ids):
+        where.setdefault(oid, j)
+    positions = [where[oid] for oid in kept]
+    z = redshifts(metadata, kept) if "Z" in metadata.columns and (NEEDS_Z & set(sets_of(mask))) else None
+    plan, strategies = RecipePlan.boone(len(kept), k, random_seed)
+    orig, copies = _run_recipe(csr, z, plan, mask, with_originals=True)
+    frame = pd.DataFrame(np.concatenate([orig, copies], axis=0), columns=columns_of(mask))
+    ids = list(kept) + boone_ids(kept, positions, plan, strategies, random_seed)
+    frame.insert(0, "object_id", ids)
+    targets = metadata["target"].to_numpy()[positions]
+    meta = pd.DataFrame({"object_id": ids, "target": np.concatenate([targets, np.repeat(targets, k)]),
+                         "original_id": list(kept) + [oid for oid in kept for _ in range(k)],
+                         "augmentation_type": ["original"] * len(kept) + list(strategies)})
+    return frame, meta
+
+
+def plasticc_augment_and_extract(train_lc, train_meta, test_meta, sets, augmentations_per_sample=5, augment_all=False, random_state=42):
+    """``augment_for_test_distribution`` (plasticc_augmentation.py:299-398) followed by the extraction of ``sets``, on the
+    device -> ``(frame, aug_meta)``, the copies only, as the reference returns them: ids ``f"{object_id}_zaug{j}"``;
+    ``aug_meta`` the object's metadata row with the new id and ``Z`` replaced by the copy's redshift, which is also what the
+    sets that read a redshift get.  TDEs only (``target == 1``) unless ``augment_all``; objects of fewer than 5 rows are
+    skipped; a NaN ``Z`` is read as 0.5; the new redshifts are drawn from the test set's."""
+    import pandas as pd
+
+    from .engine import columns_of, mask_of
+    from .packing import pack_lightcurves, select_objects
+
+    mask = mask_of(sets)
+    k = int(augmentations_per_sample)
+    test_z = test_meta["Z"].dropna()
+    picked = train_meta if augment_all else train_meta[train_meta["target"] == 1]
+    csr, kept = pack_lightcurves(train_lc, picked["object_id"].tolist())
+    long_enough = np.diff(csr["offsets"]) >= 5
+    if not long_enough.all():
+        csr, kept = select_objects(csr, kept, [oid for oid, ok in zip(kept, long_enough) if ok])
+    rows = train_meta.drop_duplicates("object_id").set_index("object_id", drop=False).loc[kept] if kept else train_meta.iloc[:0]
+    z_orig = rows["Z"].to_numpy(np.float64).copy()
+    z_orig[np.isnan(z_orig)] = 0.5
+    plan = RecipePlan.plasticc(z_orig, k, target_z=test_z.to_numpy(np.float64), random_state=random_state,
+                               z_range=(test_z.mean() - test_z.std(), test_z.mean() + test_z.std()))
+    _, copies = _run_recipe(csr, z_orig, plan, mask, with_originals=False)
+    frame = pd.DataFrame(copies, columns=columns_of(mask))
+    ids = [f"{oid}_zaug{j}" for oid in kept for j in range(k)]
+    frame.insert(0, "object_id", ids)
+    aug_meta = rows.loc[rows.index.repeat(k)].reset_index(drop=True)
+    aug_meta["object_id"] = ids
+    aug_meta["Z"] = plan.z_out
+    return frame, aug_meta
 
 
 def augmented_ids(kept_ids, n_augmentations, include_original=True):

@@ -6,6 +6,11 @@
 // every draw is a pure function of (the copy's 64-bit seed, the row's index in the INPUT object, a stream id) through
 // Philox4x32-10, so a row's values depend on neither the lane nor the workgroup nor the batch it is computed in.
 //
+// The recipe pass (RECIPE = true) is the same routine with the steps the Boone recipe (src/features/gp_augmentation.py) and
+// the PLAsTiCC recipe (src/features/plasticc_augmentation.py) add: a per-band factor on flux and error after the noise, an
+// error boost and a second noise term (stream 3) after the dropout, and Boone's keep count.  Every new step has a neutral
+// value; with all of them neutral the recipe pass writes the bytes of the plain one.
+//
 // Templates over the wave policy W as everywhere (wave.hpp): AugWave on the device -- one wavefront per input object, four
 // objects per workgroup -- and WaveHost (one lane) in the host build of the tests.
 #pragma once
@@ -29,7 +34,7 @@ LCFE_FN void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, u
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-enum { AUG_STREAM_NOISE = 0, AUG_STREAM_DROPOUT = 1, AUG_STREAM_BAND = 2 };
+enum { AUG_STREAM_NOISE = 0, AUG_STREAM_DROPOUT = 1, AUG_STREAM_BAND = 2, AUG_STREAM_NOISE2 = 3 };
 
 // the four words of (seed, row, stream): counter = (row, stream, 0, 0), key = the seed's low and high word
 LCFE_FN void aug_words(uint64_t seed, uint32_t row, uint32_t stream, uint32_t (&w)[4]) {
@@ -61,6 +66,13 @@ LCFE_FN int64_t aug_n_keep(int64_t n, double d) {
     return (m < 5) ? 5 : ((m < n) ? m : n);
 }
 LCFE_FN bool aug_dropout_valid(double d) { return d >= 0.0 && d < 1.0; }
+// the keep rules of a recipe call: 0 the rule above; 1 Boone's n - int(n d) (gp_augmentation.py:60-61), no floor
+enum { AUG_KEEP_FLOOR5 = 0, AUG_KEEP_BOONE = 1, AUG_KEEP_RULES = 2 };
+LCFE_FN int64_t aug_n_keep_rule(int64_t n, double d, int rule) {
+    if (rule == AUG_KEEP_FLOOR5) return aug_n_keep(n, d);
+    const int64_t m = n - (int64_t)((double)n * d);
+    return (m < 0) ? 0 : ((m < n) ? m : n);
+}
 
 // noise factor of a band in band_specific_noise (augmentation.py:128); an unknown filter gets none
 LCFE_FN double aug_band_scale(int b) {
@@ -77,6 +89,7 @@ struct AugIn {
     const double* add_flux;     // optional, per candidate row
     const uint8_t* keep;        // optional, per candidate row
     int k;
+    const double* add_flux2;    // recipe pass: optional, per candidate row
 };
 struct AugPlan {
     const double* scale;
@@ -86,6 +99,11 @@ struct AugPlan {
     const double* dropout;
     const uint8_t* band_noise;
     const uint64_t* seed;
+    // recipe pass; a null array is neutral throughout
+    const double* band_scale;   // [n_obj * k, 6]
+    const double* err_boost;
+    const double* noise2_scale;
+    int keep_rule;
 };
 struct AugOut {
     int64_t* offsets;
@@ -142,7 +160,7 @@ LCFE_FN bool aug_count_object(const AugIn& A, const AugPlan& P, int64_t i, doubl
         } else {
             const double d = P.dropout[o];
             ok = ok && aug_dropout_valid(d);
-            m = aug_dropout_valid(d) ? aug_n_keep(n, d) : 0;
+            m = aug_dropout_valid(d) ? aug_n_keep_rule(n, d, P.keep_rule) : 0;
         }
         if (W::lane() == 0) counts[o] = m;
     }
@@ -202,8 +220,10 @@ LCFE_FN uint64_t aug_select_key(uint64_t seed, int64_t n, int64_t rank, int* his
     return found;
 }
 
-// Pass 2 for input object i: the rows of its k copies, each compacted in file order at its offset of O.offsets.
-template <class W>
+// Pass 2 for input object i: the rows of its k copies, each compacted in file order at its offset of O.offsets.  RECIPE adds
+// the steps of the recipe pass, in the reference's order: the band factor after the first noise term, the error boost and
+// the second noise term -- in units of the boosted error -- after the selection.
+template <class W, bool RECIPE = false>
 LCFE_FN void aug_write_object(const AugIn& A, const AugPlan& P, const AugOut& O, int64_t i, const double* tmin, int* hist) {
     const int lane = W::lane();
     const int64_t r0 = A.offsets[i], n = A.offsets[i + 1] - r0;
@@ -214,6 +234,13 @@ LCFE_FN void aug_write_object(const AugIn& A, const AugPlan& P, const AugOut& O,
         const double sc = P.scale[o], st = P.stretch[o], sh = P.shift[o], ns = P.noise_scale[o];
         const bool bn = P.band_noise[o] != 0;
         const uint64_t seed = P.seed[o];
+        double bs[6] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0}, eb = 1.0, n2 = 0.0;
+        if constexpr (RECIPE) {
+            if (P.band_scale)
+                for (int j = 0; j < 6; ++j) bs[j] = P.band_scale[o * 6 + j];
+            if (P.err_boost) eb = P.err_boost[o];
+            if (P.noise2_scale) n2 = P.noise2_scale[o];
+        }
         // selection: the caller's flags, or the n_out rows with the smallest (key, row), or every row
         const bool select = !A.keep && n_out < n;
         uint64_t thr = 0;
@@ -242,11 +269,20 @@ LCFE_FN void aug_write_object(const AugIn& A, const AugPlan& P, const AugOut& O,
             if (kp && pos < n_out) {
                 const int64_t g = r0 + r;
                 double t = A.t[g], f = A.f[g] * sc;
-                const double e = A.e[g] * sc;
+                double e = A.e[g] * sc;
                 const int b = A.b[g];
                 if (st != 1.0) t = tm + (t - tm) * st;
                 if (ns != 0.0) f = f + (e * ns) * aug_normal(seed, r, AUG_STREAM_NOISE);
                 if (A.add_flux) f = f + A.add_flux[cand0 + r];
+                if constexpr (RECIPE) {
+                    if (b < 6) {
+                        const double s = (b == 0) ? bs[0] : (b == 1) ? bs[1] : (b == 2) ? bs[2] : (b == 3) ? bs[3] : (b == 4) ? bs[4] : bs[5];
+                        if (s != 1.0) { f = f * s; e = e * s; }
+                    }
+                    if (eb != 1.0) e = e * eb;
+                    if (n2 != 0.0) f = f + (e * n2) * aug_normal(seed, r, AUG_STREAM_NOISE2);
+                    if (A.add_flux2) f = f + A.add_flux2[cand0 + r];
+                }
                 if (sh != 0.0) t = t + sh;
                 if (bn && b < 6) f = f + ((e * aug_band_scale(b)) * 0.3) * aug_normal(seed, r, AUG_STREAM_BAND);
                 O.t[o0 + pos] = t;

@@ -1655,13 +1655,58 @@ __global__ __launch_bounds__(kAugScanThreads) void augment_scan_apply_kernel(int
     }
 }
 
+// RECIPE: the write pass with the steps of lcfe_augment_recipe_device (augment.hpp); the plain pass is compiled without them
+template <bool RECIPE>
 __global__ __launch_bounds__(64 * kAugWaves) void augment_write_kernel(AugIn A, AugPlan P, AugOut O, int64_t n_obj, const double* tmin,
                                                                         const int* flag) {
     __shared__ int hist[kAugWaves][64];
     if (*flag) return;                       // a bad plan: the counts are void, nothing is written
     const int64_t stride = (int64_t)gridDim.x * kAugWaves;
     for (int64_t i = (int64_t)blockIdx.x * kAugWaves + (threadIdx.x >> 6); i < n_obj; i += stride)
-        aug_write_object<AugWave>(A, P, O, i, tmin, hist[threadIdx.x >> 6]);
+        aug_write_object<AugWave, RECIPE>(A, P, O, i, tmin, hist[threadIdx.x >> 6]);
+}
+
+// the plain call and the recipe call: the same checks, the same five launches; `fn` names the entry point in the messages
+template <bool RECIPE>
+int augment_launch(const std::string& fn, int device, void* stream_, int64_t n_obj, int64_t n_points, int k, const AugIn& A,
+                          const AugPlan& P, const AugOut& O, int64_t* d_n_points_out, void* d_workspace, size_t workspace_bytes) {
+    g_err.clear();
+    if (k < 1) return fail_msg(fn + ": k must be at least 1");
+    if (n_obj < 0 || n_points < 0) return fail_msg(fn + ": negative size");
+    if (lcfe_augment_capacity(n_points, k) < 0 || n_obj > (INT64_MAX >> 4) / k) return fail_msg(fn + ": n_points * k or n_obj * k overflows");
+    if (P.keep_rule < 0 || P.keep_rule >= AUG_KEEP_RULES) return fail_msg(fn + ": unknown keep_rule " + std::to_string(P.keep_rule));
+    if (!A.offsets || !O.offsets || !d_n_points_out) return fail_msg(fn + ": null offsets or n_points_out");
+    if (n_obj > 0 && (!P.scale || !P.stretch || !P.shift || !P.noise_scale || !P.dropout || !P.band_noise || !P.seed))
+        return fail_msg(fn + ": null plan array");
+    if (n_points > 0 && (!A.t || !A.f || !A.e || !A.b || !O.t || !O.f || !O.e || !O.b)) return fail_msg(fn + ": null sample array");
+    const AugWs W(d_workspace, n_obj, k);
+    if (!d_workspace || workspace_bytes < W.bytes) return fail_msg(fn + ": workspace smaller than lcfe_augment_workspace_bytes(n_obj, k)");
+    if (W.tiles > 0x7fffffff) return fail_msg(fn + ": more than 2^42 output objects");
+    DeviceGuard guard;
+    if (guard.enter(device)) return fail_msg(fn + ": cannot select device " + std::to_string(device));
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipMemsetAsync(d_workspace, 0, kAugWsHeader, stream));
+    if (n_obj == 0) {
+        HIP_TRY(hipMemsetAsync(O.offsets, 0, sizeof(int64_t), stream));
+        HIP_TRY(hipMemsetAsync(d_n_points_out, 0, sizeof(int64_t), stream));
+        return 0;
+    }
+    const int64_t groups = (n_obj + kAugWaves - 1) / kAugWaves, cap = (int64_t)num_cus(dev) * 8;
+    const unsigned grid = (unsigned)((groups < cap) ? groups : cap);
+    const int64_t m = n_obj * k;
+    hipLaunchKernelGGL(augment_count_kernel, dim3(grid), dim3(64 * kAugWaves), 0, stream, A, P, n_obj, W.tmin, O.offsets, W.flag);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(augment_scan_tiles_kernel, dim3((unsigned)W.tiles), dim3(kAugScanThreads), 0, stream, O.offsets + 1, m, W.tile_sum);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(augment_scan_sums_kernel, dim3(1), dim3(kAugScanThreads), 0, stream, W.tile_sum, W.tiles, W.flag, d_n_points_out);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(augment_scan_apply_kernel, dim3((unsigned)W.tiles), dim3(kAugScanThreads), 0, stream, O.offsets + 1, m, W.tile_sum);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(augment_write_kernel<RECIPE>, dim3(grid), dim3(64 * kAugWaves), 0, stream, A, P, O, n_obj, W.tmin, W.flag);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // ---- sequence tensors (sequence.hpp): one wavefront per object, kSeqWaves objects per workgroup; the grid strides over
@@ -2072,46 +2117,27 @@ int lcfe_augment_device(int device, void* stream_, int64_t n_obj, int64_t n_poin
                         const uint8_t* d_band_noise, const uint64_t* d_seed, const double* d_add_flux, const uint8_t* d_keep,
                         int64_t* d_offsets_out, double* d_t_out, double* d_flux_out, double* d_err_out, uint8_t* d_band_out,
                         int64_t* d_n_points_out, void* d_workspace, size_t workspace_bytes) {
-    g_err.clear();
-    if (k < 1) return fail_msg("lcfe_augment_device: k must be at least 1");
-    if (n_obj < 0 || n_points < 0) return fail_msg("lcfe_augment_device: negative size");
-    if (lcfe_augment_capacity(n_points, k) < 0 || n_obj > (INT64_MAX >> 4) / k) return fail_msg("lcfe_augment_device: n_points * k or n_obj * k overflows");
-    if (!d_offsets || !d_offsets_out || !d_n_points_out) return fail_msg("lcfe_augment_device: null offsets or n_points_out");
-    if (n_obj > 0 && (!d_scale || !d_stretch || !d_shift || !d_noise_scale || !d_dropout || !d_band_noise || !d_seed))
-        return fail_msg("lcfe_augment_device: null plan array");
-    if (n_points > 0 && (!d_t || !d_flux || !d_err || !d_band || !d_t_out || !d_flux_out || !d_err_out || !d_band_out))
-        return fail_msg("lcfe_augment_device: null sample array");
-    const AugWs W(d_workspace, n_obj, k);
-    if (!d_workspace || workspace_bytes < W.bytes) return fail_msg("lcfe_augment_device: workspace smaller than lcfe_augment_workspace_bytes(n_obj, k)");
-    if (W.tiles > 0x7fffffff) return fail_msg("lcfe_augment_device: more than 2^42 output objects");
-    DeviceGuard guard;
-    if (guard.enter(device)) return fail_msg("lcfe_augment_device: cannot select device " + std::to_string(device));
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipMemsetAsync(d_workspace, 0, kAugWsHeader, stream));
-    if (n_obj == 0) {
-        HIP_TRY(hipMemsetAsync(d_offsets_out, 0, sizeof(int64_t), stream));
-        HIP_TRY(hipMemsetAsync(d_n_points_out, 0, sizeof(int64_t), stream));
-        return 0;
-    }
-    const AugIn A{d_offsets, d_t, d_flux, d_err, d_band, d_add_flux, d_keep, k};
-    const AugPlan P{d_scale, d_stretch, d_shift, d_noise_scale, d_dropout, d_band_noise, d_seed};
+    const AugIn A{d_offsets, d_t, d_flux, d_err, d_band, d_add_flux, d_keep, k, nullptr};
+    const AugPlan P{d_scale, d_stretch, d_shift, d_noise_scale, d_dropout, d_band_noise, d_seed, nullptr, nullptr, nullptr, AUG_KEEP_FLOOR5};
     const AugOut O{d_offsets_out, d_t_out, d_flux_out, d_err_out, d_band_out};
-    const int64_t groups = (n_obj + kAugWaves - 1) / kAugWaves, cap = (int64_t)num_cus(dev) * 8;
-    const unsigned grid = (unsigned)((groups < cap) ? groups : cap);
-    const int64_t m = n_obj * k;
-    hipLaunchKernelGGL(augment_count_kernel, dim3(grid), dim3(64 * kAugWaves), 0, stream, A, P, n_obj, W.tmin, d_offsets_out, W.flag);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(augment_scan_tiles_kernel, dim3((unsigned)W.tiles), dim3(kAugScanThreads), 0, stream, d_offsets_out + 1, m, W.tile_sum);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(augment_scan_sums_kernel, dim3(1), dim3(kAugScanThreads), 0, stream, W.tile_sum, W.tiles, W.flag, d_n_points_out);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(augment_scan_apply_kernel, dim3((unsigned)W.tiles), dim3(kAugScanThreads), 0, stream, d_offsets_out + 1, m, W.tile_sum);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(augment_write_kernel, dim3(grid), dim3(64 * kAugWaves), 0, stream, A, P, O, n_obj, W.tmin, W.flag);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return augment_launch<false>("lcfe_augment_device", device, stream_, n_obj, n_points, k, A, P, O, d_n_points_out, d_workspace,
+                                 workspace_bytes);
+}
+
+int lcfe_augment_recipe_device(int device, void* stream_, int64_t n_obj, int64_t n_points, int k, const int64_t* d_offsets,
+                               const double* d_t, const double* d_flux, const double* d_err, const uint8_t* d_band,
+                               const double* d_scale, const double* d_stretch, const double* d_shift, const double* d_noise_scale,
+                               const double* d_dropout, const uint8_t* d_band_noise, const uint64_t* d_seed,
+                               const double* d_band_scale, const double* d_err_boost, const double* d_noise2_scale, int keep_rule,
+                               const double* d_add_flux, const uint8_t* d_keep, const double* d_add_flux2, int64_t* d_offsets_out,
+                               double* d_t_out, double* d_flux_out, double* d_err_out, uint8_t* d_band_out, int64_t* d_n_points_out,
+                               void* d_workspace, size_t workspace_bytes) {
+    const AugIn A{d_offsets, d_t, d_flux, d_err, d_band, d_add_flux, d_keep, k, d_add_flux2};
+    const AugPlan P{d_scale, d_stretch, d_shift, d_noise_scale, d_dropout, d_band_noise, d_seed, d_band_scale, d_err_boost,
+                    d_noise2_scale, keep_rule};
+    const AugOut O{d_offsets_out, d_t_out, d_flux_out, d_err_out, d_band_out};
+    return augment_launch<true>("lcfe_augment_recipe_device", device, stream_, n_obj, n_points, k, A, P, O, d_n_points_out,
+                                d_workspace, workspace_bytes);
 }
 
 size_t lcfe_sequences_workspace_bytes(int64_t n_obj, int64_t n_points, int64_t max_len) {

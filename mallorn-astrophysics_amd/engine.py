@@ -156,6 +156,17 @@ class DeviceBatch:
         Explicit mode: ``add_flux`` float64 and ``keep`` uint8, host arrays over the ``n_copies * n_points`` candidate rows
         (input row ``r`` of copy ``c`` of object ``i`` at ``n_copies * offsets[i] + c * n_i + r``): ``add_flux`` is added to
         the flux after the noise step, ``keep`` replaces the dropout selection."""
+        return self._augment(plan, add_flux, keep)
+
+    def augment_recipe(self, plan, add_flux=None, keep=None, add_flux2=None):
+        """``augment`` for an ``augment.RecipePlan`` (``lcfe_augment_recipe_device``): the steps of the Boone and PLAsTiCC
+        recipes -- the per-band factor, the error boost, the second noise term, the plan's keep rule.  Where the plan has
+        ``z_out`` that is the result's ``z``; otherwise the objects' ``z`` is repeated as by ``augment``.
+
+        Explicit mode as in ``augment``; ``add_flux2`` is added to the flux after the second noise step."""
+        return self._augment(plan, add_flux, keep, add_flux2, recipe=True)
+
+    def _augment(self, plan, add_flux, keep, add_flux2=None, recipe=False):
         torch = self.torch
         lib = _lib.load()
         k = plan.n_copies
@@ -164,18 +175,27 @@ class DeviceBatch:
         cap = int(lib.lcfe_augment_capacity(self.n_points, k))
         if cap < 0:
             raise ValueError("n_points * n_copies overflows")
-        to = lambda a: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(self.device)
-        fields = [to(a) for a in plan.arrays().values()]
-
+        # a short array would be read out of bounds on the device: every shape is checked before anything is uploaded
         def explicit(a, dt, name):
             if a is None:
                 return None
             a = np.ascontiguousarray(a, dt)
-            if a.shape != (cap,):                   # a short array would be read out of bounds on the device
+            if a.shape != (cap,):
                 raise ValueError(f"{name} must have n_copies * n_points = {cap} entries")
-            return to(a)
+            return a
 
-        d_add, d_keep = explicit(add_flux, np.float64, "add_flux"), explicit(keep, np.uint8, "keep")
+        h_add, h_keep, h_add2 = explicit(add_flux, np.float64, "add_flux"), explicit(keep, np.uint8, "keep"), explicit(add_flux2, np.float64, "add_flux2")
+        extra = plan.recipe_arrays() if recipe else {}
+        if recipe:
+            m = self.n_obj * k
+            for name, a in {**plan.arrays(), **extra, **({} if plan.z_out is None else {"z_out": plan.z_out})}.items():
+                if a.shape != ((m, 6) if name == "band_scale" else (m,)) or not a.flags.c_contiguous:
+                    raise ValueError(f"{name} must have n_obj * n_copies = {m} entries")
+        to = lambda a: None if a is None else torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(self.device)
+        fields = [to(a) for a in plan.arrays().values()]
+        more = [to(a) for a in extra.values()]
+        d_add, d_keep, d_add2 = to(h_add), to(h_keep), to(h_add2)
+        z_out = to(plan.z_out) if recipe else None
         new = object.__new__(DeviceBatch)
         new.torch, new.device, new._ws = torch, self.device, None
         new.n_obj = self.n_obj * k
@@ -187,16 +207,24 @@ class DeviceBatch:
         ws = empty(wsb, torch.uint8)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
-        rc = lib.lcfe_augment_device(self.device.index, ctypes.c_void_p(stream), self.n_obj, self.n_points, k, p(self.offsets),
-                                     p(self.t), p(self.flux), p(self.err), p(self.band), *[p(a) for a in fields], p(d_add),
-                                     p(d_keep), p(new.offsets), p(t), p(flux), p(err), p(band), p(total), p(ws), wsb)
-        _lib.check(rc, "lcfe_augment_device")
+        head = (self.device.index, ctypes.c_void_p(stream), self.n_obj, self.n_points, k, p(self.offsets), p(self.t), p(self.flux),
+                p(self.err), p(self.band), *[p(a) for a in fields])
+        tail = (p(new.offsets), p(t), p(flux), p(err), p(band), p(total), p(ws), wsb)
+        if recipe:
+            what = "lcfe_augment_recipe_device"
+            rc = lib.lcfe_augment_recipe_device(*head, *[p(a) for a in more], int(plan.keep_rule), p(d_add), p(d_keep), p(d_add2), *tail)
+        else:
+            what = "lcfe_augment_device"
+            rc = lib.lcfe_augment_device(*head, p(d_add), p(d_keep), *tail)
+        _lib.check(rc, what)
         new.n_points = int(total.item())            # waits for the kernels: the row count sizes the views below
         if new.n_points < 0:
-            raise _lib.LcfeError("lcfe_augment_device: a dropout fraction of the plan lies outside [0, 1)")
+            raise _lib.LcfeError(f"{what}: a dropout fraction of the plan lies outside [0, 1)")
         new.offsets = new.offsets[:new.n_obj + 1]
         new.t, new.flux, new.err, new.band = t[:new.n_points], flux[:new.n_points], err[:new.n_points], band[:new.n_points]
         new.z = None if self.z is None else self.z.repeat_interleave(k)
+        if recipe and z_out is not None:
+            new.z = z_out
         new.max_len = int(torch.diff(new.offsets).max().item()) if new.n_obj else 0
         return new
 
