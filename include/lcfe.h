@@ -274,6 +274,42 @@ int lcfe_sequences_device(int device, void* stream, int64_t n_obj, int64_t n_poi
                           const uint8_t* d_band, float* d_features, int64_t* d_bands, float* d_mask, int64_t* d_length,
                           float* d_mean, float* d_std, void* d_workspace, size_t workspace_bytes);
 
+/*
+ * The 2-D GP's posterior mean and variance on a caller's grid (multiband_gp.py:196-247: interpolate_multiband with any epoch
+ * list, and the variance george's predict returns there): per light curve a regular time x band tensor with its uncertainty.
+ * No feature set: no mask bit, no columns.  Like lcfe_extract_device: the batch -- a staged one or the output of
+ * lcfe_augment_device -- and every d_ pointer are DEVICE pointers on `device`, the kernels are enqueued on `stream`, the call
+ * does not synchronise and allocates nothing.  `bands` is a HOST array.
+ *   grid        point (b, k) of a light curve lies at time origin + d_grid_offsets[k] (days, float64[n_times]) and at the
+ *               wavelength of band bands[b] (0..5 = u g r i z y); 1 <= n_times <= lcfe_gp2d_grid_max_times() (1024),
+ *               1 <= n_bands <= 6, bands distinct
+ *   origin      LCFE_GRID_FROM_PEAK   the gp2d set's own peak time, so offsets {0, 20, 50, 100} are the set's epochs
+ *               LCFE_GRID_FROM_FIRST  the light curve's first valid observation
+ *   d_theta_in  float64[n_obj, 4] = [mean, log c, log M0, log M1] in the set's normalised units (flux over the median |flux|):
+ *               "given" mode, one evaluation per light curve and no optimiser; NULL: "fit" mode, the fit of the gp2d set
+ *   d_mean      float64[n_obj, n_bands, n_times]: (mean + k*' K^-1 r) * flux_scale
+ *   d_var       float64[n_obj, n_bands, n_times] or NULL (the variance passes are then skipped):
+ *               (c - k*' (K + diag e2)^-1 k*) * flux_scale^2 -- no white noise on k(x*, x*), no clamp at 0, as george
+ *   d_theta_out float64[n_obj, 4]: the parameters the grid was evaluated at
+ *   d_row27     float64[n_obj, 27] or NULL, fit mode only: the gp2d set's row, byte for byte
+ *   d_status    int32[n_obj, lcfe_nstatus(1 << LCFE_SET_GP2D)], the set's words: stop reason (given mode: 0, or 5 for a
+ *               non-finite theta_in), iterations, evaluations (given mode: 0), valid points; -100 in word 0: too many rows
+ * NaN mean and var: fewer than 10 valid points, a non-finite start or parameter vector, a failed factorisation, no peak row
+ * (whatever the origin), more valid points than lcfe_gp2d_max_points().
+ * workspace: lcfe_gp2d_grid_workspace_bytes(n_obj, n_points, max_len) bytes, max_len the rows of the longest light curve.
+ * Errors (lcfe_last_error; nothing is enqueued): sizes or bands outside the limits above, an unknown origin, a NULL
+ * required array, d_row27 in given mode, a workspace that is too small.
+ */
+#define LCFE_GRID_FROM_PEAK 0
+#define LCFE_GRID_FROM_FIRST 1
+int64_t lcfe_gp2d_grid_max_times(void);
+size_t lcfe_gp2d_grid_workspace_bytes(int64_t n_obj, int64_t n_points, int64_t max_len);
+int lcfe_gp2d_grid_device(int device, void* stream, int64_t n_obj, int64_t n_points, int64_t max_len, const int64_t* d_offsets,
+                          const double* d_t, const double* d_flux, const double* d_err, const uint8_t* d_band, int n_times,
+                          const double* d_grid_offsets, int origin, int n_bands, const int* bands, const double* d_theta_in,
+                          double* d_mean, double* d_var, double* d_theta_out, double* d_row27, int32_t* d_status,
+                          void* d_workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

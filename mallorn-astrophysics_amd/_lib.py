@@ -120,6 +120,17 @@ def load():
     lib.lcfe_sequences_device.restype = ctypes.c_int
     lib.lcfe_sequences_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + \
                                          [ctypes.c_void_p] * 12 + [ctypes.c_size_t]
+    # (a library of an earlier commit, loaded through LCFE_LIB_PATH to be compared with this one, has no grid entry point:
+    #  it still loads, and DeviceBatch.gp_grid on it fails with the missing symbol's name)
+    if hasattr(lib, "lcfe_gp2d_grid_device"):
+        lib.lcfe_gp2d_grid_max_times.restype = ctypes.c_int64
+        lib.lcfe_gp2d_grid_workspace_bytes.restype = ctypes.c_size_t
+        lib.lcfe_gp2d_grid_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
+        # batch (5); n_times, offsets, origin, n_bands, bands; theta_in; mean, var, theta_out, row27, status; workspace
+        lib.lcfe_gp2d_grid_device.restype = ctypes.c_int
+        lib.lcfe_gp2d_grid_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64] + \
+                                             [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                                      ctypes.POINTER(ctypes.c_int)] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t]
     _lib = lib
     return lib
 

@@ -1071,6 +1071,156 @@ LCFE_FN_NOINLINE void gp_eval(const double* p, int n, LDS& S_arg, KP K, double& 
     GP_T(7);
 }
 
+// ---- posterior mean and variance on a caller's grid (george's predict, multiband_gp.py:236-247)
+constexpr int GP_GRID_MAX_TIMES = 1024, GP_GRID_MAX_BANDS = 6;
+constexpr int GP_GRID_COLS = 16;                           // grid columns per pass over the tiles: one MFMA operand
+enum { GP_GRID_FROM_PEAK = 0, GP_GRID_FROM_FIRST = 1 };
+// the grid of one call: point g = b * n_times + k lies at (origin + offsets[k], wavelength of band b)
+struct GpGridSpec {
+    const double* offsets;                                 // [n_times] days from the origin
+    int n_times, n_bands, origin;
+    unsigned band_codes;                                   // band b (0..5) in bits [4 b, 4 b + 4)
+    LCFE_FN int size() const { return n_times * n_bands; }
+    LCFE_FN int band(int b) const { return (int)((band_codes >> (4 * b)) & 15u); }
+};
+
+// k*' alpha at the point (tp, lp) -> `sum`: THE prediction loop, behind the set's twelve flux columns and behind every grid
+// point.  A macro over the names of its scope (W, S, lane, n, c, m0, m1), not a function: as a function -- inlined or not --
+// it changed the register allocation of every existing gp_kernel, and their code is to stay what it was.
+#define LCFE_GP_PREDICT_SUM(sum, tp, lp)                                                  \
+    double sum;                                                                           \
+    {                                                                                     \
+        double s = 0;                                                                     \
+        for (int i = lane; i < n; i += W::LANES) {                                        \
+            const double dt = tp - S.t[i], dl = lp - S.sm.lam_at(i);                      \
+            double e;                                                                     \
+            s += gp_kernel(dt * dt, dl * dl, c, m0, m1, e) * S.alpha[i];                  \
+        }                                                                                 \
+        sum = W::sum(s);                                                                  \
+    }
+
+// The grid stage: runs after gp_eval(p, n, .., need_grad = false) on the same working set, with alpha = K^-1 r in S.alpha
+// and A = -K^-1 tile-packed where the tier keeps its matrix.  mean[g] = (p[0] + k*' alpha) scale; var[g] = (c + k*' A k*)
+// scale^2 -- no white noise on k(x*, x*), no clamp at 0 (george does neither).  `var` null: the tile passes are skipped.
+// The variance takes the grid GP_GRID_COLS columns at a time.  Their kernel values K*(row, column) are written once per
+// pass into the first pivot panel S.V, which is idle after the sweep and lies where the tier keeps its working set (LDS for
+// the tiers of the table, the object's slab for the long-object tier): row-major, 16 columns per row, so that the 64 lanes
+// of an operand read touch 512 consecutive bytes.  Rows from n on (the augmented row, the identity padding) are zero in the
+// panel and so contribute exactly 0.  Every stored tile A_IJ is read once: T = A_IJ' K*_I on the fp64 MFMA -- the tile as
+// stored IS the A operand of that product --, then sum_rows K*_J o T per column; a tile below the diagonal counts twice
+// (the transposed product is never formed), a diagonal tile is mirrored from its lower half while it is loaded.  Tile rows
+// are dealt to the wavefronts in the sweep's snake and the partial sums are combined in a fixed order: the result does
+// not depend on what ran before.
+template <class W, int NP, class KP, class LDS>
+LCFE_FN void gp_grid_stage(LDS& S, KP A, int n, const double* p, double scale, double t0, const GpGridSpec& G, double* mean,
+                           double* var) {
+    const int lane = W::lane();
+    const double c = exp(p[1]), m0 = exp(p[2]), m1 = exp(p[3]);
+    const int ng = G.size();
+    for (int g = 0; g < ng; ++g) {
+        const int b = g / G.n_times, k = g - b * G.n_times;
+        const double tp = t0 + G.offsets[k], lp = gp_wavelength(G.band(b));
+        LCFE_GP_PREDICT_SUM(sum, tp, lp)
+        if (lane == 0) mean[g] = (p[0] + sum) * scale;
+    }
+    if (!var) return;
+    static_assert(GP_GRID_COLS == GP_B && NP % GP_B == 0, "one panel row per matrix row: 16 NP doubles fit S.V");
+    double* Kp = &S.V[0][0];
+    double* Sp = &S.P[0][0];
+    const int ntp = (n + GP_B - 1) >> 4;                   // tile rows that hold points
+    const double s2 = scale * scale;
+    for (int c0 = 0; c0 < ng; c0 += GP_GRID_COLS) {
+        for (int idx = lane; idx < (ntp << 8); idx += W::LANES) {
+            const int i = idx >> 4, g = c0 + (idx & 15);
+            double v = 0.0;
+            if (i < n && g < ng) {
+                const int b = g / G.n_times, k = g - b * G.n_times;
+                const double dt = t0 + G.offsets[k] - S.t[i], dl = gp_wavelength(G.band(b)) - S.sm.lam_at(i);
+                double e;
+                v = gp_kernel(dt * dt, dl * dl, c, m0, m1, e);
+            }
+            Kp[idx] = v;
+        }
+        W::sync();
+#if defined(__HIPCC__)
+        if constexpr (W::WAVE == 64) {
+            constexpr int NW = W::NWAVES;
+            static_assert(NW * GP_GRID_COLS <= GP_B * GP_B, "the wavefronts' partial sums fit S.P");
+            const int l = W::wlane(), lr = l >> 4, lc = l & 15, w = uniform_int(W::wave_id());
+            double acc = 0.0;
+            for (int blk = 0;; ++blk) {
+                const int pos = (blk & 1) ? NW - 1 - w : w;
+                const int i = ntp - 1 - (blk * NW + pos);
+                if (i < 0) break;
+                double bi[4];                                             // B operand: K*_I (k = 4 kc + lr, column lc)
+#pragma unroll
+                for (int kc = 0; kc < 4; ++kc) bi[kc] = Kp[(((i << 4) + 4 * kc + lr) << 4) + lc];
+                for (int j = 0; j <= i; ++j) {
+                    KP T = A + tile_base(i, j);
+                    double a[4];                                          // A operand: A_IJ' (row lc, k = 4 kc + lr)
+                    if (j < i) {
+#pragma unroll
+                        for (int kc = 0; kc < 4; ++kc) a[kc] = T[((4 * kc + lr) << 4) + lc];
+                    } else {
+#pragma unroll
+                        for (int kc = 0; kc < 4; ++kc) {
+                            const int r = 4 * kc + lr;
+                            a[kc] = (lc <= r) ? T[(r << 4) + lc] : T[(lc << 4) + r];
+                        }
+                    }
+                    gp_v4f64 tq = {0, 0, 0, 0};
+#pragma unroll
+                    for (int kc = 0; kc < 4; ++kc) tq = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kc], bi[kc], tq, 0, 0, 0);
+                    double s = 0.0;
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) s += tq[v] * Kp[(((j << 4) + 4 * v + lr) << 4) + lc];
+                    acc += (j < i) ? 2.0 * s : s;
+                }
+            }
+            acc += __shfl_xor(acc, 16, 64);
+            acc += __shfl_xor(acc, 32, 64);
+            if (lr == 0) Sp[(w << 4) + lc] = acc;
+            W::sync();
+            if (lane < GP_GRID_COLS && c0 + lane < ng) {
+                double q = 0.0;
+                for (int k = 0; k < NW; ++k) q += Sp[(k << 4) + lane];
+                var[c0 + lane] = (c + q) * s2;
+            }
+        } else
+#endif
+        {
+            // host simulation (one lane): the scalar twin of the tile product
+            for (int g = 0; g < GP_GRID_COLS && c0 + g < ng; ++g) {
+                double q = 0.0;
+                for (int i = 0; i < n; ++i) {
+                    double s = 0.0;
+                    for (int j = 0; j < i; ++j) s += A[tri_index(i, j)] * Kp[(j << 4) + g];
+                    q += Kp[(i << 4) + g] * (2.0 * s + A[tri_index(i, i)] * Kp[(i << 4) + g]);
+                }
+                if (lane == 0) var[c0 + g] = (c + q) * s2;
+            }
+            (void)Sp;
+        }
+        W::sync();
+    }
+}
+
+// What gp_object does besides the set's 27 columns: nothing (the gp2d set) ...
+struct GpNoTail {
+    static constexpr bool kOn = false, given = false;
+};
+// ... or the grid stage after the evaluation at the optimum (gp_grid_kernel).  given: p comes from the caller (theta_in),
+// no optimiser runs and the set's columns 5.. stay NaN.
+template <class KP>
+struct GpGridTail {
+    static constexpr bool kOn = true;
+    bool given;
+    GpGridSpec G;
+    KP K;
+    const double* theta_in;
+    double *theta_out, *mean, *var;
+};
+
 LCFE_FN bool gp_row_valid(const ObjIn& in, int i) {
     // multiband_gp.py:51-59: known band, flux and error not NaN, error > 0
     const double f = in.f[i], e = in.e[i];
@@ -1081,8 +1231,9 @@ LCFE_FN bool gp_row_valid(const ObjIn& in, int i) {
 // `K` points to packed-triangle storage for NP points (LDS or global scratch).
 // `ev(p, n, f, g, need_grad)` evaluates the objective (gp_eval with the matrix in LDS / global
 // scratch, or gp_eval_reg with the matrix in registers).
-template <class W, int NP, class Ev, class LDS>
-LCFE_FN void gp_object(const ObjIn& L, LDS& S, Ev&& gp_ev, int32_t* st) {
+// `tail` (GpNoTail, GpGridTail): what follows the evaluation at the optimum; the gp2d set passes none.
+template <class W, int NP, class Ev, class LDS, class Tail = GpNoTail>
+LCFE_FN void gp_object(const ObjIn& L, LDS& S, Ev&& gp_ev, int32_t* st, const Tail& tail = Tail()) {
     const int lane = W::lane();
     double* o = S.out;
     for (int k = lane; k < GP_NCOL; k += W::LANES) o[k] = qnan();
@@ -1153,7 +1304,12 @@ LCFE_FN void gp_object(const ObjIn& L, LDS& S, Ev&& gp_ev, int32_t* st) {
     double fval = 0;
     double xe[4] = {qnan(), qnan(), qnan(), qnan()}, fe_last = 1e25;     // the point of the optimiser's last evaluation, its objective
     int n_iter = 0, n_eval = 0, why = LB_ERROR;
-    if (finite0) {
+    if (tail.given) {
+        // the caller's parameters: status word 0 is LB_EVAL (no optimiser ran), LB_ERROR for a non-finite vector
+        if constexpr (Tail::kOn) { p[0] = tail.theta_in[0]; p[1] = tail.theta_in[1]; p[2] = tail.theta_in[2]; p[3] = tail.theta_in[3]; }
+        finite0 = finite_d(p[0]) && finite_d(p[1]) && finite_d(p[2]) && finite_d(p[3]);
+        why = finite0 ? LB_EVAL : LB_ERROR;
+    } else if (finite0) {
         // the optimiser's state machine lives in LDS and is advanced by ONE thread between two barriers:
         // none of its state is live in registers while the objective (the wide code) runs
         if (lane == 0) lb_start(S.lb, p, 100, 1e7, 1e-5, 20);
@@ -1184,6 +1340,9 @@ LCFE_FN void gp_object(const ObjIn& L, LDS& S, Ev&& gp_ev, int32_t* st) {
         p[0] = S.lb.x[0]; p[1] = S.lb.x[1]; p[2] = S.lb.x[2]; p[3] = S.lb.x[3];
     }
     if (st && lane == 0) { st[0] = why; st[1] = n_iter; st[2] = n_eval; }
+    if constexpr (Tail::kOn) {
+        if (lane == 0) { tail.theta_out[0] = p[0]; tail.theta_out[1] = p[1]; tail.theta_out[2] = p[2]; tail.theta_out[3] = p[3]; }
+    }
 #ifdef LCFE_GP_PROF
     if (st && lane == 0) for (int k = 0; k < 10; ++k) st[4 + k] = (int)(S.prof[k] >> 10);
 #endif
@@ -1226,17 +1385,14 @@ LCFE_FN void gp_object(const ObjIn& L, LDS& S, Ev&& gp_ev, int32_t* st) {
     const double EP[4] = {0, 20, 50, 100};
     const int PB[3] = {1, 2, 3};
     double fl[12];
+    if (!tail.given) {
     for (int q = 0; q < 12; ++q) {
         const double tp = peak_time + EP[q / 3], lp = gp_wavelength(PB[q % 3]);
-        double s = 0;
-        for (int i = lane; i < n; i += W::LANES) {
-            const double dt = tp - S.t[i], dl = lp - S.sm.lam_at(i);
-            double e;
-            s += gp_kernel(dt * dt, dl * dl, c, m0, m1, e) * S.alpha[i];
-        }
-        fl[q] = (p[0] + W::sum(s)) * scale;                              // :244-247
+        LCFE_GP_PREDICT_SUM(sum, tp, lp)
+        fl[q] = (p[0] + sum) * scale;                                    // :244-247
     }
-    if (lane == 0) {
+    }
+    if (!tail.given && lane == 0) {
         double gr[4];
         for (int e = 0; e < 4; ++e) {
             const double gf = fl[3 * e], rf = fl[3 * e + 1], iff = fl[3 * e + 2];
@@ -1248,7 +1404,12 @@ LCFE_FN void gp_object(const ObjIn& L, LDS& S, Ev&& gp_ev, int32_t* st) {
         o[25] = (!is_nan(gr[0]) && !is_nan(gr[2])) ? (gr[2] - gr[0]) / 50.0 : qnan();   // :265-277
         o[26] = (!is_nan(gr[0]) && !is_nan(gr[3])) ? (gr[3] - gr[0]) / 100.0 : qnan();
     }
+    if constexpr (Tail::kOn) {
+        W::sync();
+        gp_grid_stage<W, NP>(S, tail.K, n, p, scale, (tail.G.origin == GP_GRID_FROM_PEAK) ? peak_time : 0.0, tail.G, tail.mean, tail.var);
+    }
     W::sync();
 }
+#undef LCFE_GP_PREDICT_SUM
 
 }  // namespace lcfe

@@ -19,9 +19,10 @@ template <int NP> struct gp_threads { static constexpr int T = (NP == kGpLongNP)
 template <int NP> struct gp_waves { static constexpr int N = gp_tier_row(NP).waves; };
 
 // how a workgroup of NP-row capacity evaluates the objective: policy W, working set Set, matrix K addressed as a KPtr
-template <int NP, class SET, class KPTR>
+// (USER: the policy's tag -- the grid kernels evaluate on a policy of their own, BlockDev of wave.hpp)
+template <int NP, class SET, class KPTR, int USER = 0>
 struct GpEvalAs {
-    using W = BlockDev<gp_threads<NP>::T>;
+    using W = BlockDev<gp_threads<NP>::T, USER>;
     using Set = SET;
     using KPtr = KPTR;
     static __device__ __forceinline__ void eval(Set& S, double* K, const double* x, int n, double& f, double* g, bool need) {
@@ -29,9 +30,9 @@ struct GpEvalAs {
     }
 };
 // a tier of the table: working set in LDS, matrix in LDS (kLdsDoubles of the kernel's own) or in the workgroup's slab
-template <int NP, bool GLOBAL_K>
+template <int NP, bool GLOBAL_K, int USER = 0>
 struct GpTier : GpEvalAs<NP, GpLds<NP, gp_threads<NP>::T / 64, gp_tier_row(NP).fuse, true, true, gp_tier_row(NP).compact>,
-                         std::conditional_t<GLOBAL_K, global_double*, lds_double*>> {
+                         std::conditional_t<GLOBAL_K, global_double*, lds_double*>, USER> {
     static constexpr GpTierRow kRow = gp_tier_row(NP);
     static_assert(kRow.id >= 0 && kRow.global_k == GLOBAL_K, "gp_kernel<NP, GLOBAL_K> is a row of LCFE_GP_TIERS");
     static constexpr int kLdsDoubles = GLOBAL_K ? 1 : gp_store_doubles(NP);
@@ -40,10 +41,13 @@ struct GpTier : GpEvalAs<NP, GpLds<NP, gp_threads<NP>::T / 64, gp_tier_row(NP).f
 };
 // (the long tier has no pivot look-ahead: its staging tile is handed over between lanes of one wavefront under wave-level
 //  fences, which the tiers rely on for LDS only)
-struct GpLongTier : GpEvalAs<kGpLongNP, GpLds<kGpLongNP, kGpLongThreads / 64, false, false, false>, global_double*> {
+template <int USER>
+struct GpLongTierOf : GpEvalAs<kGpLongNP, GpLds<kGpLongNP, kGpLongThreads / 64, false, false, false>, global_double*, USER> {
     // slabs of the workspace: kGpLongGrid Gram matrices, then kGpLongGrid working sets
-    static constexpr size_t kSetBytes = (sizeof(Set) + 255) & ~(size_t)255;
+    static constexpr size_t kSetBytes = (sizeof(typename GpLongTierOf::Set) + 255) & ~(size_t)255;
     static constexpr size_t kBytes = (size_t)kGpLongGrid * ((size_t)gp_store_doubles(kGpLongNP) * 8 + kSetBytes);
 };
+using GpLongTier = GpLongTierOf<0>;
+constexpr int kGpGridUser = 1;         // the policy tag of gp_grid_kernel / gp_grid_long_kernel
 
 }  // namespace lcfe

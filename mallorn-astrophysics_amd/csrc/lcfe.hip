@@ -986,6 +986,65 @@ __global__ __launch_bounds__(kGpLongThreads, 1) void gp_long_kernel(BatchView B,
     }
 }
 
+// ---- the 2-D GP's posterior on a caller's grid (lcfe_gp2d_grid_device): gp_kernel's loop with the grid
+// stage as gp_object's tail, on each tier's own working set and matrix placement.  The outputs are the caller's arrays, one
+// slice per light curve; a slice is NaN until the tail has written it.
+struct GpGridOut {
+    GpGridSpec G;
+    const double* theta_in;            // [n_obj][4]; nullptr: fit mode
+    double *mean, *var, *theta_out, *row27;
+    int32_t* status;                   // [n_obj][GP_NSTATUS]
+};
+
+template <class Tier, int NP>
+__device__ __forceinline__ void gp_grid_objects(const BatchView& B, const int* list, int count, const GpGridOut& O, typename Tier::Set& S,
+                                                double* K, unsigned long long* ticket, long long& next_ticket) {
+    using W = typename Tier::W;
+    using KP = typename Tier::KPtr;
+    const int ng = O.G.size();
+    for (;;) {
+        const int64_t pos = block_ticket(ticket, next_ticket);
+        if (pos >= count) break;
+        const ListObject o = take_object(B, list, pos);
+        double* mean = O.mean + o.i * ng;
+        double* var = O.var ? O.var + o.i * ng : nullptr;
+        double* th = O.theta_out + 4 * o.i;
+        for (int g = W::lane(); g < ng; g += W::LANES) {
+            mean[g] = qnan();
+            if (var) var[g] = qnan();
+        }
+        if (W::lane() < 4) th[W::lane()] = qnan();
+        const ObjIn in = B.object(o.i, o.s, o.n, false);
+        const GpGridTail<KP> tail{O.theta_in != nullptr, O.G, (KP)K, O.theta_in ? O.theta_in + 4 * o.i : nullptr, th, mean, var};
+        gp_object<W, NP>(in, S, [&](const double* x, int n, double& f, double* g, bool need) { Tier::eval(S, K, x, n, f, g, need); },
+                         O.status + o.i * GP_NSTATUS, tail);
+        if (O.row27) store_row<W>(S.out, O.row27 + o.i * GP_NCOL, GP_NCOL);
+        __syncthreads();
+    }
+}
+
+template <int NP, bool GLOBAL_K>
+__global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP>::N)) void gp_grid_kernel(BatchView B, Bins bins, int bin, GpGridOut O,
+                                                      double* kscratch, unsigned long long* ticket) {
+    using Tier = GpTier<NP, GLOBAL_K, kGpGridUser>;
+    __shared__ typename Tier::Set S;
+    __shared__ double Klds[Tier::kLdsDoubles];
+    __shared__ long long next_ticket;
+    double* Kg = kscratch + (size_t)blockIdx.x * (size_t)gp_store_doubles(NP);
+    gp_grid_objects<Tier, NP>(B, bins.list(gp_sorted_list(bin)), bins.count(gp_list(bin)), O, S, Tier::matrix(Klds, Kg), ticket, next_ticket);
+}
+
+// the long-object tier (slabs: GpLongTier::kBytes)
+__global__ __launch_bounds__(kGpLongThreads, 1) void gp_grid_long_kernel(BatchView B, Bins bins, int bin, GpGridOut O, char* slabs,
+                                                                        unsigned long long* ticket) {
+    using Tier = GpLongTierOf<kGpGridUser>;
+    constexpr int NP = kGpLongNP;
+    __shared__ long long next_ticket;
+    double* Kg = reinterpret_cast<double*>(slabs) + (size_t)blockIdx.x * (size_t)gp_store_doubles(NP);
+    Tier::Set& S = *reinterpret_cast<Tier::Set*>(slabs + (size_t)kGpLongGrid * gp_store_doubles(NP) * 8 + (size_t)blockIdx.x * Tier::kSetBytes);
+    gp_grid_objects<Tier, NP>(B, bins.list(gp_list(bin)), bins.count(gp_list(bin)), O, S, Kg, ticket, next_ticket);
+}
+
 // The tickets of a GP tier are served longest light curve first: an evaluation costs ~N^3 and a run 10-100 evaluations, so
 // in file order the last tickets of a tier can be its most expensive light curves (a 500-row one is 60 ms on ONE workgroup
 // while the rest of the grid has drained; simulated on the bench shard, the 512-row tier ends 14 % after the ideal in file
@@ -2172,6 +2231,88 @@ int lcfe_sequences_device(int device, void* stream_, int64_t n_obj, int64_t n_po
     const unsigned grid = (unsigned)((groups < cap) ? groups : cap);
     hipLaunchKernelGGL(sequences_kernel, dim3(grid), dim3(64 * kSeqWaves), 0, (hipStream_t)stream_, A, O, n_obj, max_length, normalize);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int64_t lcfe_gp2d_grid_max_times(void) { return GP_GRID_MAX_TIMES; }
+
+// (the gp2d set's own workspace: header, index lists, the tiers' Gram-matrix slabs, the long-object tier's slabs)
+size_t lcfe_gp2d_grid_workspace_bytes(int64_t n_obj, int64_t n_points, int64_t max_len) {
+    return lcfe_workspace_bytes_for(1 << SET_GP2D, n_obj, n_points, max_len);
+}
+
+int lcfe_gp2d_grid_device(int device, void* stream_, int64_t n_obj, int64_t n_points, int64_t max_len, const int64_t* d_offsets,
+                          const double* d_t, const double* d_flux, const double* d_err, const uint8_t* d_band, int n_times,
+                          const double* d_grid_offsets, int origin, int n_bands, const int* bands, const double* d_theta_in,
+                          double* d_mean, double* d_var, double* d_theta_out, double* d_row27, int32_t* d_status, void* d_workspace,
+                          size_t workspace_bytes) {
+    g_err.clear();
+    const char* me = "lcfe_gp2d_grid_device: ";
+    if (n_times < 1 || n_times > GP_GRID_MAX_TIMES)
+        return fail_msg(std::string(me) + "n_times must lie in [1, " + std::to_string(GP_GRID_MAX_TIMES) + "]");
+    if (n_bands < 1 || n_bands > GP_GRID_MAX_BANDS || !bands) return fail_msg(std::string(me) + "n_bands must lie in [1, 6]");
+    unsigned codes = 0, seen = 0;
+    for (int b = 0; b < n_bands; ++b) {
+        if (bands[b] < 0 || bands[b] > 5) return fail_msg(std::string(me) + "a band outside 0..5");
+        if (seen & (1u << bands[b])) return fail_msg(std::string(me) + "a band is listed twice");
+        seen |= 1u << bands[b];
+        codes |= (unsigned)bands[b] << (4 * b);
+    }
+    if (origin != LCFE_GRID_FROM_PEAK && origin != LCFE_GRID_FROM_FIRST) return fail_msg(std::string(me) + "unknown origin");
+    if (n_obj < 0 || n_points < 0 || max_len < 0) return fail_msg(std::string(me) + "negative size");
+    if (n_obj > 0x7fffffff - kBinThreads) return fail_msg(std::string(me) + "more than 2^31 objects in one batch");
+    if (!d_offsets || !d_grid_offsets) return fail_msg(std::string(me) + "null offsets");
+    if (n_points > 0 && (!d_t || !d_flux || !d_err || !d_band)) return fail_msg(std::string(me) + "null sample array");
+    if (n_obj > 0 && (!d_mean || !d_theta_out || !d_status)) return fail_msg(std::string(me) + "null output array");
+    if (d_theta_in && d_row27) return fail_msg(std::string(me) + "row27 is an output of fit mode (theta_in null)");
+    if (n_obj == 0) return 0;
+    const WsLayout L(kWsSizes, 1 << SET_GP2D, n_obj, n_points, max_len, true);
+    if (!d_workspace || workspace_bytes < L.total)
+        return fail_msg(std::string(me) + "workspace smaller than lcfe_gp2d_grid_workspace_bytes(n_obj, n_points, max_len)");
+    DeviceGuard guard;
+    if (guard.enter(device)) return fail_msg(std::string(me) + "cannot select device " + std::to_string(device));
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    hipStream_t q = (hipStream_t)stream_;
+    const BatchView B{d_offsets, d_t, d_flux, d_err, d_band, nullptr, n_obj};
+    unsigned long long* tickets = (unsigned long long*)d_workspace;
+    const Bins bins{(int*)L.at(d_workspace, WS_LISTS), (int*)((char*)d_workspace + kWsCounts), n_obj};
+    const GpGridOut O{GpGridSpec{d_grid_offsets, n_times, n_bands, origin, codes}, d_theta_in, d_mean, d_var, d_theta_out, d_row27, d_status};
+    HIP_TRY(hipMemsetAsync(d_workspace, 0, kWsHeader, q));
+    hipLaunchKernelGGL(bin_kernel, dim3((unsigned)((n_obj + kBinThreads - 1) / kBinThreads)), dim3(kBinThreads), 0, q, d_offsets, n_obj,
+                       bins.lists, bins.counts);
+    HIP_TRY(hipGetLastError());
+    const int last = gp_last_tier(max_len);
+    hipLaunchKernelGGL(gp_sort_kernel, dim3((unsigned)(last + 1)), dim3(kGpSortThreads), 0, q, d_offsets, bins);
+    HIP_TRY(hipGetLastError());
+    // the set's tuning knob: LCFE_GP_GRID_<rows>=k caps the workgroups of a tier (SetLaunch::gp_tier; 2048: the long-object
+    // tier) -- with k = 1 every light curve of the tier goes through ONE workgroup, which is how the tests reach the state a
+    // workgroup carries from one light curve to the next
+    auto grid_cap = [](int np, int64_t cap) -> int64_t {
+        char name[40];
+        snprintf(name, sizeof name, "LCFE_GP_GRID_%d", np);
+        const char* e = getenv(name);
+        return (e && atoi(e) > 0 && (cap < 1 || atoi(e) < cap)) ? atoi(e) : cap;
+    };
+    // the tiers longest first on the caller's stream; every light curve is in the list of one of them or in the long list
+    for (int ti = last; ti >= 0; --ti) {
+        int rc = 0;
+        switch (ti) {
+#define X(id, NP, GK, T, WV, FUSE, COMPACT, SLABS)                                                                                   \
+    case id:                                                                                                                         \
+        rc = launch_grid(gp_grid_kernel<NP, GK>, T, {0, grid_cap(NP, GK ? SLABS : 0)}, n_obj, 1, q, dev, B, bins, ti, O,             \
+                         (double*)L.at(d_workspace, WS_GP_TIER + id), tickets + SET_GP2D * 8 + id);                                  \
+        break;
+            LCFE_GP_TIERS(X)
+#undef X
+        }
+        if (rc) return rc;
+    }
+    if (max_len > kGpLastCap) {
+        hipLaunchKernelGGL(gp_grid_long_kernel, dim3((unsigned)grid_cap(kGpLongNP, kGpLongGrid)), dim3(kGpLongThreads), 0, q, B, bins, kGpNumTiers, O,
+                           L.at(d_workspace, WS_LONG + SET_GP2D), tickets + SET_GP2D * 8 + 7);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 

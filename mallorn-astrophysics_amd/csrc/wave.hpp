@@ -223,7 +223,9 @@ struct GroupDev {
 
 // A workgroup of T threads (T/64 wavefronts) working on one object: the GP kernel's policy.
 // Reductions go through the wave shuffle network and a small LDS exchange (two barriers each).
-template <int T>
+// USER: kernel families with different tags get policies -- and with them exchange words in LDS and every function
+// instantiated on the policy -- of their own, so that adding a family leaves the code of the others as it is.
+template <int T, int USER = 0>
 struct BlockDev {
     static constexpr int LANES = T;
     static constexpr int NW = T / 64;

@@ -253,3 +253,65 @@ class DeviceBatch:
                                        p(ws), wsb)
         _lib.check(rc, "lcfe_sequences_device")
         return out
+
+    def gp_grid(self, offsets, bands=("g", "r", "i"), origin="peak", theta=None, variance=True):
+        """Posterior mean and variance of the 2-D GP of the ``gp2d`` set on a regular time x band grid, one slice per object
+        (``lcfe_gp2d_grid_device`` on the current stream).  ``offsets``: days from the origin (1 to 1024
+        of them); ``bands``: distinct names or codes 0..5; ``origin``: ``"peak"`` (the set's own peak time -- offsets
+        (0, 20, 50, 100) are the set's epochs) or ``"first"`` (the first valid observation).  ``theta`` None: fit mode, the
+        fit of the set; a float64 [n_obj, 4] array or tensor ``[mean, log c, log M0, log M1]`` (normalised units, what a
+        ``GpGrid.theta`` holds): given mode, one evaluation per object, no optimiser.  ``variance`` False skips the variance
+        passes.  Returns a ``GpGrid`` of device tensors: ``mean`` and ``var`` float64 [n_obj, n_bands, n_times] (``var`` None
+        without the variance), ``theta`` float64 [n_obj, 4], ``status`` int32 [n_obj, 4] (the set's words) and, in fit mode,
+        ``row`` float64 [n_obj, 27], the set's row.  The batch is left as it is: a staged batch and an augmented one work
+        alike."""
+        torch = self.torch
+        lib = _lib.load()
+        off = np.ascontiguousarray(np.atleast_1d(np.asarray(offsets, np.float64)))
+        if off.ndim != 1 or not 1 <= off.size <= int(lib.lcfe_gp2d_grid_max_times()):
+            raise ValueError(f"offsets must hold 1 to {int(lib.lcfe_gp2d_grid_max_times())} times")
+        codes = [GP_GRID_BANDS[b] if isinstance(b, str) else int(b) for b in bands]
+        if not 1 <= len(codes) <= 6 or len(set(codes)) != len(codes) or any(not 0 <= c <= 5 for c in codes):
+            raise ValueError("bands must be 1 to 6 distinct bands of u g r i z y (0..5)")
+        if origin not in GP_GRID_ORIGINS:
+            raise ValueError(f"origin must be one of {', '.join(GP_GRID_ORIGINS)}")
+        nt, nb = off.size, len(codes)
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        d_theta = None
+        if theta is not None:
+            d_theta = torch.as_tensor(theta, dtype=torch.float64).to(self.device).contiguous()
+            if tuple(d_theta.shape) != (self.n_obj, 4):        # a short array would be read out of bounds on the device
+                raise ValueError(f"theta must be [{self.n_obj}, 4]")
+        nst = int(lib.lcfe_nstatus(1 << SET_BITS["gp2d"]))
+        mean = new((self.n_obj, nb, nt), torch.float64)
+        var = new((self.n_obj, nb, nt), torch.float64) if variance else None
+        theta_out, status = new((self.n_obj, 4), torch.float64), torch.zeros((self.n_obj, nst), dtype=torch.int32, device=self.device)
+        row = new((self.n_obj, len(COLUMNS["gp2d"])), torch.float64) if theta is None else None
+        d_off = torch.from_numpy(off).to(self.device)
+        wsb = int(lib.lcfe_gp2d_grid_workspace_bytes(self.n_obj, self.n_points, self.max_len))
+        ws = new((max(wsb, 1),), torch.uint8)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
+        rc = lib.lcfe_gp2d_grid_device(self.device.index, ctypes.c_void_p(stream), self.n_obj, self.n_points, self.max_len, p(self.offsets),
+                                       p(self.t), p(self.flux), p(self.err), p(self.band), nt, p(d_off), GP_GRID_ORIGINS[origin], nb,
+                                       (ctypes.c_int * nb)(*codes), p(d_theta), p(mean), p(var), p(theta_out), p(row), p(status), p(ws), wsb)
+        _lib.check(rc, "lcfe_gp2d_grid_device")
+        return GpGrid(mean, var, theta_out, status, row, off, tuple(codes), origin)
+
+
+GP_GRID_BANDS = {"u": 0, "g": 1, "r": 2, "i": 3, "z": 4, "y": 5}
+GP_GRID_ORIGINS = {"peak": 0, "first": 1}          # LCFE_GRID_FROM_PEAK, LCFE_GRID_FROM_FIRST
+
+
+class GpGrid:
+    """What ``DeviceBatch.gp_grid`` returns: device tensors ``mean``, ``var`` (or None), ``theta``, ``status`` and ``row``
+    (fit mode, else None), and the grid they are on -- ``offsets`` (numpy, days), ``bands`` (codes), ``origin``."""
+
+    def __init__(self, mean, var, theta, status, row, offsets, bands, origin):
+        self.mean, self.var, self.theta, self.status, self.row = mean, var, theta, status, row
+        self.offsets, self.bands, self.origin = offsets, bands, origin
+
+    def numpy(self):
+        """The tensors as a dict of host arrays (synchronises); absent ones are None."""
+        get = lambda x: None if x is None else x.cpu().numpy()
+        return {"mean": get(self.mean), "var": get(self.var), "theta": get(self.theta), "status": get(self.status), "row": get(self.row)}

@@ -189,6 +189,25 @@ def extract_all(lightcurves=None, metadata=None, object_ids=None, sets=None, csr
     return frames
 
 
+def gp_grid(lightcurves=None, offsets=(0.0, 20.0, 50.0, 100.0), bands=("g", "r", "i"), origin="peak", theta=None, variance=True,
+            object_ids=None, csr=None, device=None):
+    """The 2-D GP's posterior on a regular time x band grid for every object of a long frame: ONE pack and ONE device call
+    (``DeviceBatch.gp_grid``; arguments as there, ``lightcurves`` / ``csr`` / ``object_ids`` as in ``extract_all``).
+    Returns a dict of host arrays -- ``mean`` and ``var`` [n_obj, n_bands, n_times] (``var`` None without the variance),
+    ``theta`` [n_obj, 4], ``status``, ``row`` (fit mode: the gp2d set's 27 columns) -- and ``object_ids``, the id order of
+    their first axis."""
+    from ..engine import DeviceBatch
+    from ..packing import select_objects
+
+    if csr is not None:
+        batch, ids = csr
+        batch, kept = (batch, list(ids)) if object_ids is None else select_objects(batch, ids, object_ids)
+    else:
+        batch, kept = pack_lightcurves(lightcurves, object_ids)
+    grid = DeviceBatch(batch, device=device).gp_grid(offsets, bands=bands, origin=origin, theta=theta, variance=variance)
+    return {**grid.numpy(), "object_ids": list(kept)}
+
+
 def run_extractor(set_name, lightcurves, object_ids=None, metadata=None, id_last=True, int_columns=()):
     """One extractor of the reference = a one-set call of ``extract_all`` (``id_last`` / ``int_columns`` are implied by
     the set and kept in the signature for the mirrors that spell them out)."""
