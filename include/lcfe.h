@@ -310,6 +310,59 @@ int lcfe_gp2d_grid_device(int device, void* stream, int64_t n_obj, int64_t n_poi
                           double* d_mean, double* d_var, double* d_theta_out, double* d_row27, int32_t* d_status,
                           void* d_workspace, size_t workspace_bytes);
 
+/*
+ * The same posterior at scattered points: per light curve a list of (t*, lambda*) pairs, lambda* ANY positive wavelength in
+ * Angstrom (a band's wavelength reproduces the grid; 5500 lies between g and r).  Everything lcfe_gp2d_grid_device says about
+ * the batch, the stream, theta_in / theta_out, row27, status, the NaN rules and the denormalisation holds here; the stage is
+ * the grid's with another column source ("Posterior at points").
+ *   d_q_off     int64[n_obj + 1], DEVICE: light curve i owns the points d_q_off[i] .. d_q_off[i + 1]; ascending from 0 to nq.
+ *               A light curve may own no point: it is fitted (row27, theta_out, status) and writes nothing else.
+ *               The call copies this array to the host ONCE, synchronising `stream`, before anything is enqueued: a list that
+ *               does not start at 0, descends or does not end at nq is an error, not an out-of-bounds store.  It is the only
+ *               synchronisation of the call.
+ *   d_q_t       float64[nq]: days from the origin (LCFE_GRID_FROM_PEAK / LCFE_GRID_FROM_FIRST, the grid's two origins)
+ *   d_q_lam     float64[nq]: Angstrom
+ *   want_var    0: the variance passes are skipped and d_var is not touched
+ *   d_mean, d_var   float64[nq]
+ * A point with a non-finite time, or a wavelength that is non-finite or <= 0, is NaN in mean and var and leaves every other
+ * point what it is without it.  A light curve without a GP (see above) is NaN at all its points.
+ * workspace: lcfe_gp2d_points_workspace_bytes_for(n_obj, n_points, max_len) bytes.
+ * Errors (lcfe_last_error; nothing is enqueued): an unknown origin, a negative size, a NULL required array, d_row27 in given
+ * mode, a workspace that is too small, a d_q_off as described.
+ */
+size_t lcfe_gp2d_points_workspace_bytes_for(int64_t n_obj, int64_t n_points, int64_t max_len);
+int lcfe_gp2d_points_device(int device, void* stream, int64_t n_obj, int64_t n_points, int64_t max_len, const int64_t* d_offsets,
+                            const double* d_t, const double* d_flux, const double* d_err, const uint8_t* d_band, int64_t nq,
+                            const int64_t* d_q_off, const double* d_q_t, const double* d_q_lam, int origin, const double* d_theta_in,
+                            int want_var, double* d_mean, double* d_var, double* d_theta_out, double* d_row27, int32_t* d_status,
+                            void* d_workspace, size_t workspace_bytes);
+
+/*
+ * GP-resampled copies: the two passes around lcfe_gp2d_points_device (fit mode on the SOURCE batch) that
+ * turn the copies an augmentation call produced into copies whose fluxes are drawn from the source's GP posterior at another
+ * redshift.  The copies of source o are objects o k .. o k + k - 1 of the copy batch (what lcfe_augment_device writes); a
+ * copy keeps its rows (t, band, err).  Device pointers, `stream`, no synchronisation, no workspace.  This recipe has no
+ * counterpart in the reference.
+ * query: per row r of the copy batch (copy c of source o), s = (1 + z_new[c]) / (1 + z_old[o]):
+ *   d_q_t[r] = (t_r - shift[c] - t_ref[o]) / s, d_q_lam[r] = lambda_band(r) / s (3670 4825 6222 7545 8691 9710 A); NaN both for
+ *   a row of filter 255.  t_ref: the gp2d set's peak row's time (LCFE_GRID_FROM_PEAK) or the first valid observation
+ *   (LCFE_GRID_FROM_FIRST) of the source; NaN where there is none.  d_q_off[o] = d_copy_offsets[o k], int64[n_src + 1]:
+ *   point r is row r.  s = 1 and shift = 0 give the row's own time in the origin's frame and its band's wavelength, exactly.
+ * write: with mu, var the points stage's outputs at the queries, sd = sqrt(max(var, 0)):
+ *   flux = dim (mu + sd n1) + (err noise) n2;  err_out = sqrt(err^2 (1 + noise^2) + (dim sd)^2);  NaN both where mu or var is NaN.
+ *   d_n1, d_n2 float64 per row (explicit mode) or both NULL: Philox4x32-10 streams 4 and 5, key d_seed[c], counter (the row's
+ *   index in its copy, stream, 0, 0), the Box-Muller of lcfe_augment_device.  d_status_out[c] = word 0 of the source's status.
+ * Errors: k < 1, a negative size, an unknown origin, n_copies not a multiple of k, one of n1 / n2 alone, a NULL required array.
+ */
+int lcfe_gp_resample_query_device(int device, void* stream, int64_t n_src, int k, int origin, const int64_t* d_offsets, const double* d_t,
+                                  const double* d_flux, const double* d_err, const uint8_t* d_band, const double* d_z_old,
+                                  const int64_t* d_copy_offsets, const double* d_copy_t, const uint8_t* d_copy_band, const double* d_z_new,
+                                  const double* d_shift, int64_t* d_q_off, double* d_q_t, double* d_q_lam);
+int lcfe_gp_resample_write_device(int device, void* stream, int64_t n_copies, int k, const int64_t* d_copy_offsets, const double* d_copy_err,
+                                  const double* d_mean, const double* d_var, const double* d_dim, const double* d_noise, const uint64_t* d_seed,
+                                  const double* d_n1, const double* d_n2, const int32_t* d_src_status, int n_status, double* d_flux_out,
+                                  double* d_err_out, int32_t* d_status_out);
+
 #ifdef __cplusplus
 }
 #endif

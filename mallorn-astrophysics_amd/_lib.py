@@ -131,6 +131,23 @@ def load():
         lib.lcfe_gp2d_grid_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64] + \
                                              [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                                       ctypes.POINTER(ctypes.c_int)] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t]
+    if hasattr(lib, "lcfe_gp2d_points_device"):
+        lib.lcfe_gp2d_points_workspace_bytes_for.restype = ctypes.c_size_t
+        lib.lcfe_gp2d_points_workspace_bytes_for.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
+        # batch (5); nq, q_off, q_t, q_lam, origin; theta_in; want_var; mean, var, theta_out, row27, status; workspace
+        lib.lcfe_gp2d_points_device.restype = ctypes.c_int
+        lib.lcfe_gp2d_points_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64] + \
+                                               [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p,
+                                                                                                                    ctypes.c_int] + \
+                                               [ctypes.c_void_p] * 6 + [ctypes.c_size_t]
+    if hasattr(lib, "lcfe_gp_resample_query_device"):
+        # n_src, k, origin; source batch (5), z_old; copy offsets, t, band; z_new, shift; q_off, q_t, q_lam
+        lib.lcfe_gp_resample_query_device.restype = ctypes.c_int
+        lib.lcfe_gp_resample_query_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 14
+        # n_copies, k; copy offsets, err; mean, var; dim, noise, seed; n1, n2; source status, n_status; flux, err, status
+        lib.lcfe_gp_resample_write_device.restype = ctypes.c_int
+        lib.lcfe_gp_resample_write_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 10 + \
+                                                     [ctypes.c_int] + [ctypes.c_void_p] * 3
     _lib = lib
     return lib
 

@@ -196,6 +196,119 @@ class RecipePlan(AugmentPlan):
                    noise2_scale=(boost - 1) / boost, keep_rule=KEEP_FLOOR5, z_out=z_new)
 
 
+GP_WAVELENGTHS = np.array([3670.0, 4825.0, 6222.0, 7545.0, 8691.0, 9710.0])      # multiband_gp.py:26-29, u g r i z y
+
+
+class GpResamplePlan:
+    """The per-copy plan of ``DeviceBatch.gp_resample`` ("GP-resampled copies"; no counterpart in the
+    reference): float64 arrays of one entry per copy ``o * k + c`` -- ``z_new`` (the copy's redshift), ``dim`` (factor on the
+    GP's flux), ``noise`` (white noise in units of the row's error) and ``shift`` (days: the shift the copy's rows already
+    carry, taken off again before the source's GP is asked) -- and ``seed`` (uint64, Philox mode).  ``z_old``: the sources'
+    redshifts when the builder knows them; else the source batch's ``z`` is used."""
+
+    def __init__(self, z_new, dim, noise, shift, seed=None, z_old=None):
+        f = lambda a: np.ascontiguousarray(a, np.float64).ravel()
+        self.z_new, self.dim, self.noise, self.shift = f(z_new), f(dim), f(noise), f(shift)
+        m = self.z_new.size
+        self.seed = np.arange(m, dtype=np.uint64) if seed is None else np.ascontiguousarray(seed, np.uint64).ravel()
+        self.z_old = None if z_old is None else f(z_old)
+        if any(a.size != m for a in (self.dim, self.noise, self.shift, self.seed)):
+            raise ValueError("z_new, dim, noise, shift and seed must have one entry per copy")
+
+    @classmethod
+    def redshift(cls, z_old, z_new, noise=0.0, shift=0.0, seed=None):
+        """Copies of sources at ``z_old`` [n_obj] moved to ``z_new`` [n_obj, k] (or [n_obj * k]): ``dim`` is the squared ratio
+        of luminosity distances times ``(1 + z_new) / (1 + z_old)`` -- ``luminosity_distance`` is the restatement
+        ``RecipePlan.plasticc`` uses, with its ``+ 1e-10``."""
+        z_old = np.ascontiguousarray(z_old, np.float64).ravel()
+        z_new = np.ascontiguousarray(z_new, np.float64)
+        if z_old.size == 0 or z_new.size % z_old.size:
+            raise ValueError("z_new must hold the same number of copies for every object")
+        zo = np.repeat(z_old, z_new.size // z_old.size)
+        zn = z_new.ravel()
+        dim = ((luminosity_distance(zo) + 1e-10) / (luminosity_distance(zn) + 1e-10)) ** 2 * ((1 + zn) / (1 + zo))
+        full = lambda v: np.broadcast_to(np.asarray(v, np.float64), zn.shape).copy()
+        return cls(zn, dim, full(noise), full(shift), seed=seed, z_old=z_old)
+
+    @classmethod
+    def neutral(cls, n_obj, n_copies, z=None):
+        """s = 1, dim = 1, no noise, no shift: the copies get the source's posterior mean at their own rows."""
+        z = np.zeros(n_obj) if z is None else np.ascontiguousarray(z, np.float64)
+        m = n_obj * n_copies
+        return cls(np.repeat(z, n_copies), np.ones(m), np.zeros(m), np.zeros(m), z_old=z)
+
+
+def gp_resample_queries(copy_offsets, copy_t, copy_band, k, z_old, t_ref, plan):
+    """numpy restatement of the query pass: ``(q_t, q_lam)`` per row of the copy batch, the device's float64 operations."""
+    n = np.diff(np.asarray(copy_offsets))
+    per_row = lambda a: np.repeat(np.asarray(a, np.float64), n)
+    s = per_row((1.0 + plan.z_new) / (1.0 + np.repeat(np.asarray(z_old, np.float64), k)))
+    known = np.asarray(copy_band) < 6
+    lam = GP_WAVELENGTHS[np.where(known, copy_band, 0)]
+    with np.errstate(all="ignore"):
+        q_t = np.where(known, (np.asarray(copy_t, np.float64) - per_row(plan.shift) - per_row(np.repeat(t_ref, k))) / s, np.nan)
+        q_lam = np.where(known, lam / s, np.nan)
+    return q_t, q_lam
+
+
+def gp_resample_rows(copy_offsets, copy_err, mean, var, plan, n1, n2):
+    """numpy restatement of the write pass: ``(flux, err)`` per row, the device's float64 operations in its order."""
+    n = np.diff(np.asarray(copy_offsets))
+    dim, noise = np.repeat(plan.dim, n), np.repeat(plan.noise, n)
+    e = np.asarray(copy_err, np.float64)
+    with np.errstate(all="ignore"):
+        sd = np.sqrt(np.where(var > 0.0, var, 0.0))
+        ds = dim * sd
+        flux = dim * (mean + sd * n1) + (e * noise) * n2
+        err = np.sqrt((e * e) * (1.0 + noise * noise) + ds * ds)
+    bad = np.isnan(mean) | np.isnan(var)
+    return np.where(bad, np.nan, flux), np.where(bad, np.nan, err)
+
+
+def gp_augment_and_extract(lightcurves, metadata, sets, K=3, z_range=(0.1, 1.5), noise=0.0, dropout=0.0, random_state=42, origin="peak"):
+    """K GP-resampled copies per object at redshifts drawn uniformly from ``z_range``, and the extraction of ``sets``, on the
+    device: pack once, one ``augment`` (identity rows, thinned by ``dropout``), one ``gp_resample``, one engine call ->
+    ``(frame, meta)`` as ``boone_augment_and_extract`` returns them: the originals first, then per object its copies, ids
+    ``<id>_gpz<c>``; ``meta`` has ``object_id, target, original_id, augmentation_type`` (``'original'`` / ``'gp_redshift'``)
+    ``Z`` = ``z_new`` for the copies and ``gp_status`` (word 0 of the source's GP status for a copy, 0 for an original).
+    ``metadata`` needs ``object_id``, ``target`` and ``Z``.  No counterpart in the
+    reference (its GP recipe never reads the GP at another wavelength)."""
+    import pandas as pd
+
+    from .engine import DeviceBatch, columns_of, mask_of
+    from .features._frame import redshifts
+    from .packing import pack_lightcurves
+
+    mask = mask_of(sets)
+    k = int(K)
+    object_ids = metadata["object_id"].tolist()
+    csr, kept = pack_lightcurves(lightcurves, object_ids)
+    where = {}
+    for j, oid in enumerate(object_ids):
+        where.setdefault(oid, j)
+    positions = [where[oid] for oid in kept]
+    z = np.ascontiguousarray(redshifts(metadata, kept), np.float64)
+    rng = np.random.RandomState(random_state)
+    m = len(kept) * k
+    plan = GpResamplePlan.redshift(z, rng.uniform(z_range[0], z_range[1], m), noise=noise, seed=_seeds(rng, m))
+    rows = AugmentPlan.identity(len(kept), k)
+    rows.dropout[:] = dropout
+    rows.seed[:] = _seeds(rng, m)
+    source = DeviceBatch(csr, z=z)
+    copies = source.gp_resample(source.augment(rows), plan, origin=origin)
+    orig = source.run(mask)[0].cpu().numpy()
+    out = copies.run(mask)[0].cpu().numpy()
+    frame = pd.DataFrame(np.concatenate([orig, out], axis=0), columns=columns_of(mask))
+    ids = list(kept) + [f"{oid}_gpz{c}" for oid in kept for c in range(k)]
+    frame.insert(0, "object_id", ids)
+    targets = metadata["target"].to_numpy()[positions]
+    meta = pd.DataFrame({"object_id": ids, "target": np.concatenate([targets, np.repeat(targets, k)]),
+                         "original_id": list(kept) + [oid for oid in kept for _ in range(k)],
+                         "augmentation_type": ["original"] * len(kept) + ["gp_redshift"] * m, "Z": np.concatenate([z, plan.z_new]),
+                         "gp_status": np.concatenate([np.zeros(len(kept), np.int32), copies.gp_status.cpu().numpy()])})
+    return frame, meta
+
+
 def boone_ids(kept_ids, positions, plan, strategies, random_seed=42):
     """Ids of the copies as ``augment_single_object`` names them (gp_augmentation.py:117, 122, 127, 142): ``_shift{int(d):+d}``,
     ``_sparse{int(100 frac)}``, ``_noise{int(10 f)}`` and, for ``combined``, ``_aug{random_seed + i k + c}`` with ``i`` =

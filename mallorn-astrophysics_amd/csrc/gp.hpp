@@ -1082,6 +1082,26 @@ struct GpGridSpec {
     unsigned band_codes;                                   // band b (0..5) in bits [4 b, 4 b + 4)
     LCFE_FN int size() const { return n_times * n_bands; }
     LCFE_FN int band(int b) const { return (int)((band_codes >> (4 * b)) & 15u); }
+    // column g of the stage: its time in the frame of origin t0 and its wavelength; false: the column has no point
+    LCFE_FN bool column(int g, double t0, double& tp, double& lp) const {
+        const int b = g / n_times, k = g - b * n_times;
+        tp = t0 + offsets[k];
+        lp = gp_wavelength(band(b));
+        return true;
+    }
+};
+// the other column source: a list of caller points (t*, lambda*), lambda* any positive wavelength in Angstrom.  A point
+// with a non-finite time or a wavelength that is non-finite or <= 0 has no column: NaN mean and variance.
+struct GpPointSpec {
+    const double *t, *lam;                                 // [n] days from the origin, Angstrom
+    int n, origin;
+    LCFE_FN int size() const { return n; }
+    LCFE_FN bool column(int g, double t0, double& tp, double& lp) const {
+        const double tq = t[g];
+        lp = lam[g];
+        tp = t0 + tq;
+        return finite_d(tq) && finite_d(lp) && lp > 0.0;
+    }
 };
 
 // k*' alpha at the point (tp, lp) -> `sum`: THE prediction loop, behind the set's twelve flux columns and behind every grid
@@ -1111,15 +1131,21 @@ struct GpGridSpec {
 // (the transposed product is never formed), a diagonal tile is mirrored from its lower half while it is loaded.  Tile rows
 // are dealt to the wavefronts in the sweep's snake and the partial sums are combined in a fixed order: the result does
 // not depend on what ran before.
-template <class W, int NP, class KP, class LDS>
-LCFE_FN void gp_grid_stage(LDS& S, KP A, int n, const double* p, double scale, double t0, const GpGridSpec& G, double* mean,
+// `G` is the column source (GpGridSpec: the regular grid; GpPointSpec: a point list): it says where column g lies and
+// whether it lies anywhere -- a column without a point is NaN in mean and var and all zeros in the panel, so that the
+// other columns of its pass are what they are without it.
+template <class W, int NP, class KP, class LDS, class Src>
+LCFE_FN void gp_grid_stage(LDS& S, KP A, int n, const double* p, double scale, double t0, const Src& G, double* mean,
                            double* var) {
     const int lane = W::lane();
     const double c = exp(p[1]), m0 = exp(p[2]), m1 = exp(p[3]);
     const int ng = G.size();
     for (int g = 0; g < ng; ++g) {
-        const int b = g / G.n_times, k = g - b * G.n_times;
-        const double tp = t0 + G.offsets[k], lp = gp_wavelength(G.band(b));
+        double tp, lp;
+        if (!G.column(g, t0, tp, lp)) {
+            if (lane == 0) mean[g] = qnan();
+            continue;
+        }
         LCFE_GP_PREDICT_SUM(sum, tp, lp)
         if (lane == 0) mean[g] = (p[0] + sum) * scale;
     }
@@ -1134,10 +1160,12 @@ LCFE_FN void gp_grid_stage(LDS& S, KP A, int n, const double* p, double scale, d
             const int i = idx >> 4, g = c0 + (idx & 15);
             double v = 0.0;
             if (i < n && g < ng) {
-                const int b = g / G.n_times, k = g - b * G.n_times;
-                const double dt = t0 + G.offsets[k] - S.t[i], dl = gp_wavelength(G.band(b)) - S.sm.lam_at(i);
-                double e;
-                v = gp_kernel(dt * dt, dl * dl, c, m0, m1, e);
+                double tp, lp;
+                if (G.column(g, t0, tp, lp)) {
+                    const double dt = tp - S.t[i], dl = lp - S.sm.lam_at(i);
+                    double e;
+                    v = gp_kernel(dt * dt, dl * dl, c, m0, m1, e);
+                }
             }
             Kp[idx] = v;
         }
@@ -1184,7 +1212,8 @@ LCFE_FN void gp_grid_stage(LDS& S, KP A, int n, const double* p, double scale, d
             if (lane < GP_GRID_COLS && c0 + lane < ng) {
                 double q = 0.0;
                 for (int k = 0; k < NW; ++k) q += Sp[(k << 4) + lane];
-                var[c0 + lane] = (c + q) * s2;
+                double tp, lp;
+                var[c0 + lane] = G.column(c0 + lane, t0, tp, lp) ? (c + q) * s2 : qnan();
             }
         } else
 #endif
@@ -1197,7 +1226,8 @@ LCFE_FN void gp_grid_stage(LDS& S, KP A, int n, const double* p, double scale, d
                     for (int j = 0; j < i; ++j) s += A[tri_index(i, j)] * Kp[(j << 4) + g];
                     q += Kp[(i << 4) + g] * (2.0 * s + A[tri_index(i, i)] * Kp[(i << 4) + g]);
                 }
-                if (lane == 0) var[c0 + g] = (c + q) * s2;
+                double tp, lp;
+                if (lane == 0) var[c0 + g] = G.column(c0 + g, t0, tp, lp) ? (c + q) * s2 : qnan();
             }
             (void)Sp;
         }
@@ -1211,11 +1241,11 @@ struct GpNoTail {
 };
 // ... or the grid stage after the evaluation at the optimum (gp_grid_kernel).  given: p comes from the caller (theta_in),
 // no optimiser runs and the set's columns 5.. stay NaN.
-template <class KP>
+template <class KP, class Src = GpGridSpec>
 struct GpGridTail {
     static constexpr bool kOn = true;
     bool given;
-    GpGridSpec G;
+    Src G;                             // the column source: GpGridSpec or GpPointSpec
     KP K;
     const double* theta_in;
     double *theta_out, *mean, *var;
@@ -1406,7 +1436,11 @@ LCFE_FN void gp_object(const ObjIn& L, LDS& S, Ev&& gp_ev, int32_t* st, const Ta
     }
     if constexpr (Tail::kOn) {
         W::sync();
-        gp_grid_stage<W, NP>(S, tail.K, n, p, scale, (tail.G.origin == GP_GRID_FROM_PEAK) ? peak_time : 0.0, tail.G, tail.mean, tail.var);
+        // Every lane gets the origin from lane 0 (which always holds a row; every return above is taken by all lanes).  The
+        // predictions above use only the lanes that hold a row, the stage's panel fill uses all of them: nothing a lane
+        // without a row carries may reach the fill ("The origin reaches every lane through LDS").
+        const double t0 = W::bcast_from_first_wave((tail.G.origin == GP_GRID_FROM_PEAK) ? peak_time : 0.0);
+        gp_grid_stage<W, NP>(S, tail.K, n, p, scale, t0, tail.G, tail.mean, tail.var);
     }
     W::sync();
 }

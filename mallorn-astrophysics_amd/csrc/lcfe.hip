@@ -26,6 +26,7 @@
 #include "gp_tiers.hpp"
 #include "gp1d_tiers.hpp"
 #include "augment.hpp"
+#include "gp_resample.hpp"
 #include "sequence.hpp"
 
 using namespace lcfe;
@@ -994,20 +995,45 @@ struct GpGridOut {
     const double* theta_in;            // [n_obj][4]; nullptr: fit mode
     double *mean, *var, *theta_out, *row27;
     int32_t* status;                   // [n_obj][GP_NSTATUS]
+    // the column source of light curve i and where its columns start in mean and var
+    using Src = GpGridSpec;
+    static constexpr const char* kWorkspaceFn = "lcfe_gp2d_grid_workspace_bytes";
+    __device__ __forceinline__ Src source(int64_t i, int64_t& base) const {
+        base = i * G.size();
+        return G;
+    }
+};
+// ... and at a caller's points (lcfe_gp2d_points_device): light curve i has the columns q_off[i] .. q_off[i + 1] of q_t and
+// q_lam, and of mean and var
+struct GpPointsOut {
+    const int64_t* q_off;              // [n_obj + 1]
+    const double *q_t, *q_lam;
+    int origin;
+    const double* theta_in;
+    double *mean, *var, *theta_out, *row27;
+    int32_t* status;
+    using Src = GpPointSpec;
+    static constexpr const char* kWorkspaceFn = "lcfe_gp2d_points_workspace_bytes_for";
+    __device__ __forceinline__ Src source(int64_t i, int64_t& base) const {
+        base = q_off[i];
+        return GpPointSpec{q_t + base, q_lam + base, (int)(q_off[i + 1] - base), origin};
+    }
 };
 
-template <class Tier, int NP>
-__device__ __forceinline__ void gp_grid_objects(const BatchView& B, const int* list, int count, const GpGridOut& O, typename Tier::Set& S,
+template <class Tier, int NP, class Out>
+__device__ __forceinline__ void gp_grid_objects(const BatchView& B, const int* list, int count, const Out& O, typename Tier::Set& S,
                                                 double* K, unsigned long long* ticket, long long& next_ticket) {
     using W = typename Tier::W;
     using KP = typename Tier::KPtr;
-    const int ng = O.G.size();
     for (;;) {
         const int64_t pos = block_ticket(ticket, next_ticket);
         if (pos >= count) break;
         const ListObject o = take_object(B, list, pos);
-        double* mean = O.mean + o.i * ng;
-        double* var = O.var ? O.var + o.i * ng : nullptr;
+        int64_t base;
+        const typename Out::Src G = O.source(o.i, base);
+        const int ng = G.size();
+        double* mean = O.mean + base;
+        double* var = O.var ? O.var + base : nullptr;
         double* th = O.theta_out + 4 * o.i;
         for (int g = W::lane(); g < ng; g += W::LANES) {
             mean[g] = qnan();
@@ -1015,7 +1041,7 @@ __device__ __forceinline__ void gp_grid_objects(const BatchView& B, const int* l
         }
         if (W::lane() < 4) th[W::lane()] = qnan();
         const ObjIn in = B.object(o.i, o.s, o.n, false);
-        const GpGridTail<KP> tail{O.theta_in != nullptr, O.G, (KP)K, O.theta_in ? O.theta_in + 4 * o.i : nullptr, th, mean, var};
+        const GpGridTail<KP, typename Out::Src> tail{O.theta_in != nullptr, G, (KP)K, O.theta_in ? O.theta_in + 4 * o.i : nullptr, th, mean, var};
         gp_object<W, NP>(in, S, [&](const double* x, int n, double& f, double* g, bool need) { Tier::eval(S, K, x, n, f, g, need); },
                          O.status + o.i * GP_NSTATUS, tail);
         if (O.row27) store_row<W>(S.out, O.row27 + o.i * GP_NCOL, GP_NCOL);
@@ -1023,8 +1049,8 @@ __device__ __forceinline__ void gp_grid_objects(const BatchView& B, const int* l
     }
 }
 
-template <int NP, bool GLOBAL_K>
-__global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP>::N)) void gp_grid_kernel(BatchView B, Bins bins, int bin, GpGridOut O,
+template <int NP, bool GLOBAL_K, class Out>
+__global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP>::N)) void gp_grid_kernel(BatchView B, Bins bins, int bin, Out O,
                                                       double* kscratch, unsigned long long* ticket) {
     using Tier = GpTier<NP, GLOBAL_K, kGpGridUser>;
     __shared__ typename Tier::Set S;
@@ -1035,13 +1061,14 @@ __global__ __launch_bounds__(gp_threads<NP>::T, (gp_waves<NP>::N)) void gp_grid_
 }
 
 // the long-object tier (slabs: GpLongTier::kBytes)
-__global__ __launch_bounds__(kGpLongThreads, 1) void gp_grid_long_kernel(BatchView B, Bins bins, int bin, GpGridOut O, char* slabs,
+template <class Out>
+__global__ __launch_bounds__(kGpLongThreads, 1) void gp_grid_long_kernel(BatchView B, Bins bins, int bin, Out O, char* slabs,
                                                                         unsigned long long* ticket) {
     using Tier = GpLongTierOf<kGpGridUser>;
     constexpr int NP = kGpLongNP;
     __shared__ long long next_ticket;
     double* Kg = reinterpret_cast<double*>(slabs) + (size_t)blockIdx.x * (size_t)gp_store_doubles(NP);
-    Tier::Set& S = *reinterpret_cast<Tier::Set*>(slabs + (size_t)kGpLongGrid * gp_store_doubles(NP) * 8 + (size_t)blockIdx.x * Tier::kSetBytes);
+    typename Tier::Set& S = *reinterpret_cast<typename Tier::Set*>(slabs + (size_t)kGpLongGrid * gp_store_doubles(NP) * 8 + (size_t)blockIdx.x * Tier::kSetBytes);
     gp_grid_objects<Tier, NP>(B, bins.list(gp_list(bin)), bins.count(gp_list(bin)), O, S, Kg, ticket, next_ticket);
 }
 
@@ -1778,6 +1805,76 @@ __global__ __launch_bounds__(64 * kSeqWaves) void sequences_kernel(SeqIn A, SeqO
         seq_object<WaveOfBlock>(A, O, i, max_length, normalize != 0);
 }
 
+// What lcfe_gp2d_grid_device and lcfe_gp2d_points_device enqueue once their arguments are checked: binning, the sort, and
+// the tiers' kernels with `O` (GpGridOut, GpPointsOut) as their column source and outputs.
+template <class Out>
+int gp_grid_enqueue(const char* me, int device, hipStream_t q, int64_t n_obj, int64_t n_points, int64_t max_len, const BatchView& B,
+                    const Out& O, void* d_workspace, size_t workspace_bytes) {
+    const WsLayout L(kWsSizes, 1 << SET_GP2D, n_obj, n_points, max_len, true);
+    if (!d_workspace || workspace_bytes < L.total)
+        return fail_msg(std::string(me) + "workspace smaller than " + Out::kWorkspaceFn + "(n_obj, n_points, max_len)");
+    DeviceGuard guard;
+    if (guard.enter(device)) return fail_msg(std::string(me) + "cannot select device " + std::to_string(device));
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    unsigned long long* tickets = (unsigned long long*)d_workspace;
+    const Bins bins{(int*)L.at(d_workspace, WS_LISTS), (int*)((char*)d_workspace + kWsCounts), n_obj};
+    HIP_TRY(hipMemsetAsync(d_workspace, 0, kWsHeader, q));
+    hipLaunchKernelGGL(bin_kernel, dim3((unsigned)((n_obj + kBinThreads - 1) / kBinThreads)), dim3(kBinThreads), 0, q, B.offsets, n_obj,
+                       bins.lists, bins.counts);
+    HIP_TRY(hipGetLastError());
+    const int last = gp_last_tier(max_len);
+    hipLaunchKernelGGL(gp_sort_kernel, dim3((unsigned)(last + 1)), dim3(kGpSortThreads), 0, q, B.offsets, bins);
+    HIP_TRY(hipGetLastError());
+    // the set's tuning knob: LCFE_GP_GRID_<rows>=k caps the workgroups of a tier (SetLaunch::gp_tier; 2048: the long-object
+    // tier) -- with k = 1 every light curve of the tier goes through ONE workgroup, which is how the tests reach the state a
+    // workgroup carries from one light curve to the next
+    auto grid_cap = [](int np, int64_t cap) -> int64_t {
+        char name[40];
+        snprintf(name, sizeof name, "LCFE_GP_GRID_%d", np);
+        const char* e = getenv(name);
+        return (e && atoi(e) > 0 && (cap < 1 || atoi(e) < cap)) ? atoi(e) : cap;
+    };
+    // the tiers longest first on the caller's stream; every light curve is in the list of one of them or in the long list
+    for (int ti = last; ti >= 0; --ti) {
+        int rc = 0;
+        switch (ti) {
+#define X(id, NP, GK, T, WV, FUSE, COMPACT, SLABS)                                                                                   \
+    case id:                                                                                                                         \
+        rc = launch_grid(gp_grid_kernel<NP, GK, Out>, T, {0, grid_cap(NP, GK ? SLABS : 0)}, n_obj, 1, q, dev, B, bins, ti, O,             \
+                         (double*)L.at(d_workspace, WS_GP_TIER + id), tickets + SET_GP2D * 8 + id);                                  \
+        break;
+            LCFE_GP_TIERS(X)
+#undef X
+        }
+        if (rc) return rc;
+    }
+    if (max_len > kGpLastCap) {
+        hipLaunchKernelGGL(gp_grid_long_kernel<Out>, dim3((unsigned)grid_cap(kGpLongNP, kGpLongGrid)), dim3(kGpLongThreads), 0, q, B, bins, kGpNumTiers, O,
+                           L.at(d_workspace, WS_LONG + SET_GP2D), tickets + SET_GP2D * 8 + 7);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// ---- GP-resampled copies (gp_resample.hpp): one wavefront per source object (query) or per copy (write), kAugWaves of them
+// per workgroup; the grids stride.  No LDS and no workspace.
+__global__ __launch_bounds__(64 * kAugWaves) void gp_resample_query_kernel(GpResSource S, GpResCopies C, GpResPlan P, int64_t n_src, int origin,
+                                                                         int64_t* q_off, double* q_t, double* q_lam) {
+    const int64_t stride = (int64_t)gridDim.x * kAugWaves;
+    for (int64_t o = (int64_t)blockIdx.x * kAugWaves + (threadIdx.x >> 6); o < n_src; o += stride)
+        gp_res_query_object<AugWave>(S, C, P, o, n_src, origin, q_off, q_t, q_lam);
+}
+
+__global__ __launch_bounds__(64 * kAugWaves) void gp_resample_write_kernel(GpResCopies C, GpResPlan P, int64_t n_copies, const double* mean,
+                                                                         const double* var, const double* n1, const double* n2,
+                                                                         const int32_t* src_status, int nst, double* flux_out, double* err_out,
+                                                                         int32_t* status_out) {
+    const int64_t stride = (int64_t)gridDim.x * kAugWaves;
+    for (int64_t oc = (int64_t)blockIdx.x * kAugWaves + (threadIdx.x >> 6); oc < n_copies; oc += stride)
+        gp_res_write_copy<AugWave>(C, P, oc, mean, var, n1, n2, src_status, nst, flux_out, err_out, status_out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2266,53 +2363,105 @@ int lcfe_gp2d_grid_device(int device, void* stream_, int64_t n_obj, int64_t n_po
     if (n_obj > 0 && (!d_mean || !d_theta_out || !d_status)) return fail_msg(std::string(me) + "null output array");
     if (d_theta_in && d_row27) return fail_msg(std::string(me) + "row27 is an output of fit mode (theta_in null)");
     if (n_obj == 0) return 0;
-    const WsLayout L(kWsSizes, 1 << SET_GP2D, n_obj, n_points, max_len, true);
-    if (!d_workspace || workspace_bytes < L.total)
-        return fail_msg(std::string(me) + "workspace smaller than lcfe_gp2d_grid_workspace_bytes(n_obj, n_points, max_len)");
+    const BatchView B{d_offsets, d_t, d_flux, d_err, d_band, nullptr, n_obj};
+    const GpGridOut O{GpGridSpec{d_grid_offsets, n_times, n_bands, origin, codes}, d_theta_in, d_mean, d_var, d_theta_out, d_row27, d_status};
+    return gp_grid_enqueue(me, device, (hipStream_t)stream_, n_obj, n_points, max_len, B, O, d_workspace, workspace_bytes);
+}
+
+size_t lcfe_gp2d_points_workspace_bytes_for(int64_t n_obj, int64_t n_points, int64_t max_len) {
+    return lcfe_workspace_bytes_for(1 << SET_GP2D, n_obj, n_points, max_len);
+}
+
+int lcfe_gp2d_points_device(int device, void* stream_, int64_t n_obj, int64_t n_points, int64_t max_len, const int64_t* d_offsets,
+                            const double* d_t, const double* d_flux, const double* d_err, const uint8_t* d_band, int64_t nq,
+                            const int64_t* d_q_off, const double* d_q_t, const double* d_q_lam, int origin, const double* d_theta_in,
+                            int want_var, double* d_mean, double* d_var, double* d_theta_out, double* d_row27, int32_t* d_status,
+                            void* d_workspace, size_t workspace_bytes) {
+    g_err.clear();
+    const char* me = "lcfe_gp2d_points_device: ";
+    if (origin != LCFE_GRID_FROM_PEAK && origin != LCFE_GRID_FROM_FIRST) return fail_msg(std::string(me) + "unknown origin");
+    if (n_obj < 0 || n_points < 0 || max_len < 0 || nq < 0) return fail_msg(std::string(me) + "negative size");
+    if (n_obj > 0x7fffffff - kBinThreads) return fail_msg(std::string(me) + "more than 2^31 objects in one batch");
+    if (!d_offsets || !d_q_off) return fail_msg(std::string(me) + "null offsets");
+    if (n_points > 0 && (!d_t || !d_flux || !d_err || !d_band)) return fail_msg(std::string(me) + "null sample array");
+    if (nq > 0 && (!d_q_t || !d_q_lam)) return fail_msg(std::string(me) + "null point array");
+    if (n_obj > 0 && (!d_theta_out || !d_status)) return fail_msg(std::string(me) + "null output array");
+    if (nq > 0 && (!d_mean || (want_var && !d_var))) return fail_msg(std::string(me) + "null output array");
+    if (d_theta_in && d_row27) return fail_msg(std::string(me) + "row27 is an output of fit mode (theta_in null)");
+    if (n_obj > 0 && (!d_workspace || workspace_bytes < lcfe_gp2d_points_workspace_bytes_for(n_obj, n_points, max_len)))
+        return fail_msg(std::string(me) + "workspace smaller than lcfe_gp2d_points_workspace_bytes_for(n_obj, n_points, max_len)");
+    // q_off lives on the device: ONE blocking copy of the whole array (8 (n_obj + 1) bytes) before anything is enqueued, so
+    // that a list that is not ascending from 0 to nq, or an object with 2^31 points, is an error here and not an
+    // out-of-bounds store there
+    DeviceGuard guard;
+    if (guard.enter(device)) return fail_msg(std::string(me) + "cannot select device " + std::to_string(device));
+    hipStream_t q = (hipStream_t)stream_;
+    std::vector<int64_t> qo((size_t)n_obj + 1);
+    HIP_TRY(hipMemcpyAsync(qo.data(), d_q_off, qo.size() * sizeof(int64_t), hipMemcpyDeviceToHost, q));
+    HIP_TRY(hipStreamSynchronize(q));
+    if (qo[0] != 0) return fail_msg(std::string(me) + "q_off[0] must be 0");
+    for (int64_t i = 0; i < n_obj; ++i) {
+        if (qo[i + 1] < qo[i]) return fail_msg(std::string(me) + "q_off must not descend");
+        if (qo[i + 1] - qo[i] > 0x7fffffff) return fail_msg(std::string(me) + "more than 2^31 points of one light curve");
+    }
+    if (qo[n_obj] != nq) return fail_msg(std::string(me) + "q_off[n_obj] must equal nq");
+    if (n_obj == 0) return 0;
+    const BatchView B{d_offsets, d_t, d_flux, d_err, d_band, nullptr, n_obj};
+    const GpPointsOut O{d_q_off, d_q_t, d_q_lam, origin, d_theta_in, d_mean, want_var ? d_var : nullptr, d_theta_out, d_row27, d_status};
+    return gp_grid_enqueue(me, device, q, n_obj, n_points, max_len, B, O, d_workspace, workspace_bytes);
+}
+
+int lcfe_gp_resample_query_device(int device, void* stream_, int64_t n_src, int k, int origin, const int64_t* d_offsets, const double* d_t,
+                                  const double* d_flux, const double* d_err, const uint8_t* d_band, const double* d_z_old,
+                                  const int64_t* d_copy_offsets, const double* d_copy_t, const uint8_t* d_copy_band, const double* d_z_new,
+                                  const double* d_shift, int64_t* d_q_off, double* d_q_t, double* d_q_lam) {
+    g_err.clear();
+    const char* me = "lcfe_gp_resample_query_device: ";
+    if (k < 1) return fail_msg(std::string(me) + "k must be at least 1");
+    if (n_src < 0) return fail_msg(std::string(me) + "negative size");
+    if (origin != LCFE_GRID_FROM_PEAK && origin != LCFE_GRID_FROM_FIRST) return fail_msg(std::string(me) + "unknown origin");
+    if (!d_offsets || !d_copy_offsets || !d_q_off) return fail_msg(std::string(me) + "null offsets");
+    if (n_src > 0 && (!d_t || !d_flux || !d_err || !d_band || !d_z_old || !d_copy_t || !d_copy_band || !d_z_new || !d_shift || !d_q_t || !d_q_lam))
+        return fail_msg(std::string(me) + "null array");
+    if (n_src == 0) return 0;
     DeviceGuard guard;
     if (guard.enter(device)) return fail_msg(std::string(me) + "cannot select device " + std::to_string(device));
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    hipStream_t q = (hipStream_t)stream_;
-    const BatchView B{d_offsets, d_t, d_flux, d_err, d_band, nullptr, n_obj};
-    unsigned long long* tickets = (unsigned long long*)d_workspace;
-    const Bins bins{(int*)L.at(d_workspace, WS_LISTS), (int*)((char*)d_workspace + kWsCounts), n_obj};
-    const GpGridOut O{GpGridSpec{d_grid_offsets, n_times, n_bands, origin, codes}, d_theta_in, d_mean, d_var, d_theta_out, d_row27, d_status};
-    HIP_TRY(hipMemsetAsync(d_workspace, 0, kWsHeader, q));
-    hipLaunchKernelGGL(bin_kernel, dim3((unsigned)((n_obj + kBinThreads - 1) / kBinThreads)), dim3(kBinThreads), 0, q, d_offsets, n_obj,
-                       bins.lists, bins.counts);
+    const GpResSource S{d_offsets, d_t, d_flux, d_err, d_band, d_z_old};
+    const GpResCopies C{d_copy_offsets, d_copy_t, nullptr, d_copy_band, k};
+    const GpResPlan P{d_z_new, nullptr, nullptr, d_shift, nullptr};
+    const int64_t blocks = std::min<int64_t>((n_src + kAugWaves - 1) / kAugWaves, (int64_t)num_cus(dev) * 8);
+    hipLaunchKernelGGL(gp_resample_query_kernel, dim3((unsigned)blocks), dim3(64 * kAugWaves), 0, (hipStream_t)stream_, S, C, P, n_src, origin,
+                       d_q_off, d_q_t, d_q_lam);
     HIP_TRY(hipGetLastError());
-    const int last = gp_last_tier(max_len);
-    hipLaunchKernelGGL(gp_sort_kernel, dim3((unsigned)(last + 1)), dim3(kGpSortThreads), 0, q, d_offsets, bins);
+    return 0;
+}
+
+int lcfe_gp_resample_write_device(int device, void* stream_, int64_t n_copies, int k, const int64_t* d_copy_offsets, const double* d_copy_err,
+                                  const double* d_mean, const double* d_var, const double* d_dim, const double* d_noise, const uint64_t* d_seed,
+                                  const double* d_n1, const double* d_n2, const int32_t* d_src_status, int n_status, double* d_flux_out,
+                                  double* d_err_out, int32_t* d_status_out) {
+    g_err.clear();
+    const char* me = "lcfe_gp_resample_write_device: ";
+    if (k < 1) return fail_msg(std::string(me) + "k must be at least 1");
+    if (n_copies < 0 || n_copies % k != 0) return fail_msg(std::string(me) + "n_copies must be a multiple of k");
+    if (n_status < 1) return fail_msg(std::string(me) + "n_status must be at least 1");
+    if ((d_n1 == nullptr) != (d_n2 == nullptr)) return fail_msg(std::string(me) + "n1 and n2 come together (explicit mode) or not at all");
+    if (!d_n1 && !d_seed) return fail_msg(std::string(me) + "Philox mode needs the seeds");
+    if (!d_copy_offsets || !d_copy_err || !d_mean || !d_var || !d_dim || !d_noise || !d_src_status || !d_flux_out || !d_err_out || !d_status_out)
+        return fail_msg(std::string(me) + "null array");
+    if (n_copies == 0) return 0;
+    DeviceGuard guard;
+    if (guard.enter(device)) return fail_msg(std::string(me) + "cannot select device " + std::to_string(device));
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const GpResCopies C{d_copy_offsets, nullptr, d_copy_err, nullptr, k};
+    const GpResPlan P{nullptr, d_dim, d_noise, nullptr, d_seed ? d_seed : (const uint64_t*)d_dim};
+    const int64_t blocks = std::min<int64_t>((n_copies + kAugWaves - 1) / kAugWaves, (int64_t)num_cus(dev) * 8);
+    hipLaunchKernelGGL(gp_resample_write_kernel, dim3((unsigned)blocks), dim3(64 * kAugWaves), 0, (hipStream_t)stream_, C, P, n_copies, d_mean, d_var,
+                       d_n1, d_n2, d_src_status, n_status, d_flux_out, d_err_out, d_status_out);
     HIP_TRY(hipGetLastError());
-    // the set's tuning knob: LCFE_GP_GRID_<rows>=k caps the workgroups of a tier (SetLaunch::gp_tier; 2048: the long-object
-    // tier) -- with k = 1 every light curve of the tier goes through ONE workgroup, which is how the tests reach the state a
-    // workgroup carries from one light curve to the next
-    auto grid_cap = [](int np, int64_t cap) -> int64_t {
-        char name[40];
-        snprintf(name, sizeof name, "LCFE_GP_GRID_%d", np);
-        const char* e = getenv(name);
-        return (e && atoi(e) > 0 && (cap < 1 || atoi(e) < cap)) ? atoi(e) : cap;
-    };
-    // the tiers longest first on the caller's stream; every light curve is in the list of one of them or in the long list
-    for (int ti = last; ti >= 0; --ti) {
-        int rc = 0;
-        switch (ti) {
-#define X(id, NP, GK, T, WV, FUSE, COMPACT, SLABS)                                                                                   \
-    case id:                                                                                                                         \
-        rc = launch_grid(gp_grid_kernel<NP, GK>, T, {0, grid_cap(NP, GK ? SLABS : 0)}, n_obj, 1, q, dev, B, bins, ti, O,             \
-                         (double*)L.at(d_workspace, WS_GP_TIER + id), tickets + SET_GP2D * 8 + id);                                  \
-        break;
-            LCFE_GP_TIERS(X)
-#undef X
-        }
-        if (rc) return rc;
-    }
-    if (max_len > kGpLastCap) {
-        hipLaunchKernelGGL(gp_grid_long_kernel, dim3((unsigned)grid_cap(kGpLongNP, kGpLongGrid)), dim3(kGpLongThreads), 0, q, B, bins, kGpNumTiers, O,
-                           L.at(d_workspace, WS_LONG + SET_GP2D), tickets + SET_GP2D * 8 + 7);
-        HIP_TRY(hipGetLastError());
-    }
     return 0;
 }
 

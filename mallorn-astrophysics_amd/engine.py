@@ -299,6 +299,110 @@ class DeviceBatch:
         return GpGrid(mean, var, theta_out, status, row, off, tuple(codes), origin)
 
 
+    def gp_points(self, q_off, q_t, q_lam, origin="peak", theta=None, variance=True):
+        """Posterior mean and variance of the 2-D GP of the ``gp2d`` set at scattered points, a list per object
+        (``lcfe_gp2d_points_device`` on the current stream; DESIGN.md section 9, "Posterior at points").  Object ``i`` owns
+        the points ``q_off[i]:q_off[i + 1]`` of ``q_t`` (days from the origin, ``"peak"`` or ``"first"`` as in ``gp_grid``)
+        and ``q_lam`` (wavelength in Angstrom, any positive value).  ``q_off`` int64 [n_obj + 1] ascending from 0 to
+        ``len(q_t)``; arrays or tensors, tensors on the batch's device are used as they are.  ``theta``, ``variance`` as in
+        ``gp_grid``.  Returns a ``GpPoints`` of device tensors: ``mean`` and ``var`` float64 [nq] (``var`` None without the
+        variance), ``theta``, ``status`` and, in fit mode, ``row``.  A point with a non-finite time or a wavelength that is
+        not a positive finite number is NaN; so are all points of an object without a GP.  The call reads ``q_off`` back once
+        to check it (one synchronisation of the current stream)."""
+        torch = self.torch
+        lib = _lib.load()
+        if origin not in GP_GRID_ORIGINS:
+            raise ValueError(f"origin must be one of {', '.join(GP_GRID_ORIGINS)}")
+        dev = lambda x, dt: torch.as_tensor(x, dtype=dt).to(self.device).contiguous().reshape(-1)
+        d_off, d_t, d_lam = dev(q_off, torch.int64), dev(q_t, torch.float64), dev(q_lam, torch.float64)
+        nq = int(d_t.numel())
+        if int(d_off.numel()) != self.n_obj + 1:              # a short array would be read out of bounds
+            raise ValueError(f"q_off must hold {self.n_obj + 1} offsets")
+        if int(d_lam.numel()) != nq:
+            raise ValueError("q_t and q_lam must have one length")
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        d_theta = None
+        if theta is not None:
+            d_theta = torch.as_tensor(theta, dtype=torch.float64).to(self.device).contiguous()
+            if tuple(d_theta.shape) != (self.n_obj, 4):
+                raise ValueError(f"theta must be [{self.n_obj}, 4]")
+        nst = int(lib.lcfe_nstatus(1 << SET_BITS["gp2d"]))
+        mean = new((nq,), torch.float64)
+        var = new((nq,), torch.float64) if variance else None
+        theta_out, status = new((self.n_obj, 4), torch.float64), torch.zeros((self.n_obj, nst), dtype=torch.int32, device=self.device)
+        row = new((self.n_obj, len(COLUMNS["gp2d"])), torch.float64) if theta is None else None
+        wsb = int(lib.lcfe_gp2d_points_workspace_bytes_for(self.n_obj, self.n_points, self.max_len))
+        ws = new((max(wsb, 1),), torch.uint8)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
+        rc = lib.lcfe_gp2d_points_device(self.device.index, ctypes.c_void_p(stream), self.n_obj, self.n_points, self.max_len, p(self.offsets),
+                                         p(self.t), p(self.flux), p(self.err), p(self.band), nq, p(d_off), p(d_t), p(d_lam),
+                                         GP_GRID_ORIGINS[origin], p(d_theta), 1 if variance else 0, p(mean), p(var), p(theta_out), p(row),
+                                         p(status), p(ws), wsb)
+        _lib.check(rc, "lcfe_gp2d_points_device")
+        return GpPoints(mean, var, theta_out, status, row, d_off, origin)
+
+
+    def gp_resample(self, copies, plan, explicit=None, origin="peak"):
+        """GP-resampled copies: ``copies`` is what ``self.augment`` / ``self.augment_recipe`` returned
+        (k copies per object of this batch, rows shifted and thinned); ``plan`` a ``GpResamplePlan``.  Every copy keeps its
+        rows ``(t, band, err)``; its flux becomes ``dim (mu* + sd n1) + err noise n2`` and its error ``sqrt(err^2 (1 + noise^2)
+        + (dim sd)^2)`` with ``mu*``, ``sd^2`` this batch's GP posterior (fit mode) at ``t* = (t - shift - t_ref) / s``,
+        ``lambda* = lambda_band / s``, ``s = (1 + z_new) / (1 + z_old)``.  ``explicit``: ``(n1, n2)`` float64 per row of
+        ``copies``; None: Philox streams 4 and 5 under ``plan.seed``.  ``z_old`` is ``plan.z_old`` or this batch's ``z``.
+        Returns a ``DeviceBatch`` that shares ``offsets``, ``t`` and ``band`` with ``copies``; its ``z`` is ``plan.z_new``,
+        ``gp_status`` (int32 per copy) word 0 of the source's GP status, ``gp_points`` the ``GpPoints`` it was written from
+        and ``q_t`` / ``q_lam`` the queries.  A row whose point is NaN (unknown filter, source without a GP) gets NaN flux and
+        error."""
+        torch = self.torch
+        lib = _lib.load()
+        if origin not in GP_GRID_ORIGINS:
+            raise ValueError(f"origin must be one of {', '.join(GP_GRID_ORIGINS)}")
+        if self.n_obj < 1 or copies.n_obj % self.n_obj:
+            raise ValueError("copies must hold the same number of copies of every object of this batch")
+        k = copies.n_obj // self.n_obj
+        m = copies.n_obj
+        if plan.z_new.size != m:
+            raise ValueError(f"the plan is for {plan.z_new.size} copies, the batch has {m}")
+        to = lambda a: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(self.device)     # (plan arrays are contiguous)
+        if plan.z_old is not None:
+            z_old = to(plan.z_old)
+        elif self.z is not None:
+            z_old = self.z.to(torch.float64).contiguous()
+        else:
+            raise ValueError("the sources' redshifts are needed: a plan with z_old or a batch staged with z")
+        if int(z_old.numel()) != self.n_obj:
+            raise ValueError(f"z_old must hold {self.n_obj} redshifts")
+        z_new, dim, noise, shift, seed = to(plan.z_new), to(plan.dim), to(plan.noise), to(plan.shift), to(plan.seed)
+        nq = copies.n_points
+        d_n1 = d_n2 = None
+        if explicit is not None:
+            d_n1, d_n2 = (torch.as_tensor(a, dtype=torch.float64).to(self.device).contiguous().reshape(-1) for a in explicit)
+            if int(d_n1.numel()) != nq or int(d_n2.numel()) != nq:           # a short array would be read out of bounds
+                raise ValueError(f"explicit n1 and n2 must have one entry per row of the copies ({nq})")
+        new = lambda n, dt: torch.empty(max(int(n), 1), dtype=dt, device=self.device)
+        q_off, q_t, q_lam = new(self.n_obj + 1, torch.int64), new(nq, torch.float64), new(nq, torch.float64)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
+        rc = lib.lcfe_gp_resample_query_device(self.device.index, ctypes.c_void_p(stream), self.n_obj, k, GP_GRID_ORIGINS[origin], p(self.offsets),
+                                               p(self.t), p(self.flux), p(self.err), p(self.band), p(z_old), p(copies.offsets), p(copies.t),
+                                               p(copies.band), p(z_new), p(shift), p(q_off), p(q_t), p(q_lam))
+        _lib.check(rc, "lcfe_gp_resample_query_device")
+        pts = self.gp_points(q_off[:self.n_obj + 1], q_t[:nq], q_lam[:nq], origin=origin)
+        flux, err, status = new(nq, torch.float64), new(nq, torch.float64), new(m, torch.int32)
+        rc = lib.lcfe_gp_resample_write_device(self.device.index, ctypes.c_void_p(stream), m, k, p(copies.offsets), p(copies.err), p(pts.mean),
+                                               p(pts.var), p(dim), p(noise), p(seed), p(d_n1), p(d_n2), p(pts.status),
+                                               int(pts.status.shape[1]), p(flux), p(err), p(status))
+        _lib.check(rc, "lcfe_gp_resample_write_device")
+        out = object.__new__(DeviceBatch)
+        out.torch, out.device, out._ws = torch, self.device, None
+        out.n_obj, out.n_points, out.max_len = copies.n_obj, copies.n_points, copies.max_len
+        out.offsets, out.t, out.band = copies.offsets, copies.t, copies.band
+        out.flux, out.err, out.z = flux[:nq], err[:nq], z_new
+        out.gp_status, out.gp_points, out.q_t, out.q_lam = status[:m], pts, q_t[:nq], q_lam[:nq]
+        return out
+
+
 GP_GRID_BANDS = {"u": 0, "g": 1, "r": 2, "i": 3, "z": 4, "y": 5}
 GP_GRID_ORIGINS = {"peak": 0, "first": 1}          # LCFE_GRID_FROM_PEAK, LCFE_GRID_FROM_FIRST
 
@@ -315,3 +419,17 @@ class GpGrid:
         """The tensors as a dict of host arrays (synchronises); absent ones are None."""
         get = lambda x: None if x is None else x.cpu().numpy()
         return {"mean": get(self.mean), "var": get(self.var), "theta": get(self.theta), "status": get(self.status), "row": get(self.row)}
+
+
+class GpPoints:
+    """What ``DeviceBatch.gp_points`` returns: device tensors ``mean``, ``var`` (or None) [nq], ``theta``, ``status``, ``row``
+    (fit mode, else None), and ``q_off`` (device, int64 [n_obj + 1]): object ``i`` owns ``mean[q_off[i]:q_off[i + 1]]``."""
+
+    def __init__(self, mean, var, theta, status, row, q_off, origin):
+        self.mean, self.var, self.theta, self.status, self.row, self.q_off, self.origin = mean, var, theta, status, row, q_off, origin
+
+    def numpy(self):
+        """The tensors as a dict of host arrays (synchronises); absent ones are None."""
+        get = lambda x: None if x is None else x.cpu().numpy()
+        return {"mean": get(self.mean), "var": get(self.var), "theta": get(self.theta), "status": get(self.status), "row": get(self.row),
+                "q_off": get(self.q_off)}

@@ -208,6 +208,24 @@ def gp_grid(lightcurves=None, offsets=(0.0, 20.0, 50.0, 100.0), bands=("g", "r",
     return {**grid.numpy(), "object_ids": list(kept)}
 
 
+def gp_points(lightcurves=None, q_off=None, q_t=None, q_lam=None, origin="peak", theta=None, variance=True, object_ids=None, csr=None,
+              device=None):
+    """The 2-D GP's posterior at scattered (time, wavelength) points for every object of a long frame: ONE pack and ONE
+    device call (``DeviceBatch.gp_points``; arguments as there -- ``q_off`` in the order of the returned ``object_ids`` --,
+    ``lightcurves`` / ``csr`` / ``object_ids`` as in ``extract_all``).  Returns a dict of host arrays -- ``mean`` and
+    ``var`` [nq] (``var`` None without the variance), ``theta``, ``status``, ``row``, ``q_off`` -- and ``object_ids``."""
+    from ..engine import DeviceBatch
+    from ..packing import select_objects
+
+    if csr is not None:
+        batch, ids = csr
+        batch, kept = (batch, list(ids)) if object_ids is None else select_objects(batch, ids, object_ids)
+    else:
+        batch, kept = pack_lightcurves(lightcurves, object_ids)
+    pts = DeviceBatch(batch, device=device).gp_points(q_off, q_t, q_lam, origin=origin, theta=theta, variance=variance)
+    return {**pts.numpy(), "object_ids": list(kept)}
+
+
 def run_extractor(set_name, lightcurves, object_ids=None, metadata=None, id_last=True, int_columns=()):
     """One extractor of the reference = a one-set call of ``extract_all`` (``id_last`` / ``int_columns`` are implied by
     the set and kept in the signature for the mirrors that spell them out)."""
