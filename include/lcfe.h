@@ -338,6 +338,35 @@ int lcfe_gp2d_points_device(int device, void* stream, int64_t n_obj, int64_t n_p
                             void* d_workspace, size_t workspace_bytes);
 
 /*
+ * Posterior mean and standard deviation of the PER-BAND GP of set `gp1d` at a caller's times ("Per-band
+ * GP posterior"; reference: gaussian_process.py, interpolate_at_times -> predict(return_std=True)).  No set, no mask bit:
+ * an entry point of its own beside lcfe_gp2d_points_device.  Batch arguments as lcfe_extract_device.
+ *   d_q_off     int64[n_obj + 1], DEVICE: light curve i owns the queries d_q_off[i] .. d_q_off[i + 1], in any order; checked
+ *               on the host as lcfe_gp2d_points_device checks its list (ONE synchronisation of `stream`)
+ *   d_q_t       float64[nq]: MJD, the light curve's own time axis
+ *   d_q_band    uint8[nq]: 1..4 = g, r, i, z
+ *   d_theta_in  float64[n_obj][4][3] (log c, log l, log s2) per band: given mode -- no optimiser, one evaluation; a non-finite
+ *               theta skips the band.  NULL: fit mode -- the set's own fit, then one evaluation at the winning theta
+ *   d_mean, d_std   float64[nq], in the caller's query order, in the reference's units (standardised flux):
+ *               x* = clip((t* - t_min) / t_range, 0, 1), mean = k*' K^-1 y, std = sqrt(max(c + s2 - k*' K^-1 k*, 0))
+ *   d_theta_out float64[n_obj][4][3]: the theta the posterior was read at (fit mode: the best of the four runs)
+ *   d_norm      float64[n_obj][4][4]: (t_min, t_range, f_mean, f_std) per band; flux = mean f_std + f_mean
+ *   d_cols      float64[n_obj][16]: the four per-band columns of set `gp1d` (fit mode: the set's own bytes)
+ *   d_status    int32[n_obj][4]: the set's status words (given mode: 1 evaluation)
+ * NaN, never an error: a band the reference does not fit, a band of more than lcfe_gp1d_max_points() valid rows, a query
+ * with a non-finite time or a band code outside 1..4 -- which leaves every other query what it is without it.
+ * workspace: lcfe_gp1d_points_workspace_bytes_for(n_obj, n_points, max_len, nq) bytes.
+ * Errors (lcfe_last_error; nothing is enqueued): a negative size, a NULL required array, a workspace that is too small, a
+ * d_q_off as described.
+ */
+size_t lcfe_gp1d_points_workspace_bytes_for(int64_t n_obj, int64_t n_points, int64_t max_len, int64_t nq);
+int lcfe_gp1d_points_device(int device, void* stream, int64_t n_obj, int64_t n_points, int64_t max_len, const int64_t* d_offsets,
+                            const double* d_t, const double* d_flux, const double* d_err, const uint8_t* d_band, int64_t nq,
+                            const int64_t* d_q_off, const double* d_q_t, const uint8_t* d_q_band, const double* d_theta_in,
+                            double* d_mean, double* d_std, double* d_theta_out, double* d_norm, double* d_cols, int32_t* d_status,
+                            void* d_workspace, size_t workspace_bytes);
+
+/*
  * GP-resampled copies: the two passes around lcfe_gp2d_points_device (fit mode on the SOURCE batch) that
  * turn the copies an augmentation call produced into copies whose fluxes are drawn from the source's GP posterior at another
  * redshift.  The copies of source o are objects o k .. o k + k - 1 of the copy batch (what lcfe_augment_device writes); a

@@ -140,6 +140,13 @@ def load():
                                                [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p,
                                                                                                                     ctypes.c_int] + \
                                                [ctypes.c_void_p] * 6 + [ctypes.c_size_t]
+    if hasattr(lib, "lcfe_gp1d_points_device"):
+        lib.lcfe_gp1d_points_workspace_bytes_for.restype = ctypes.c_size_t
+        lib.lcfe_gp1d_points_workspace_bytes_for.argtypes = [ctypes.c_int64] * 4
+        # batch (5); nq, q_off, q_t, q_band; theta_in; mean, std, theta_out, norm, cols, status; workspace
+        lib.lcfe_gp1d_points_device.restype = ctypes.c_int
+        lib.lcfe_gp1d_points_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64] + \
+                                               [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_void_p] * 11 + [ctypes.c_size_t]
     if hasattr(lib, "lcfe_gp_resample_query_device"):
         # n_src, k, origin; source batch (5), z_old; copy offsets, t, band; z_new, shift; q_off, q_t, q_lam
         lib.lcfe_gp_resample_query_device.restype = ctypes.c_int

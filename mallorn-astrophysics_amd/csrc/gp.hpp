@@ -1134,20 +1134,46 @@ struct GpPointSpec {
 // `G` is the column source (GpGridSpec: the regular grid; GpPointSpec: a point list): it says where column g lies and
 // whether it lies anywhere -- a column without a point is NaN in mean and var and all zeros in the panel, so that the
 // other columns of its pass are what they are without it.
+// GpStageModel<Src> is the model the source's columns belong to: the kernel value between a column and row i of the
+// working set, the prior variance at a column, what becomes of the posterior variance, and where column g's results go.
+// The 2-D sources share the one below; the per-band GP's source (gp1d_points.hpp) brings its own -- a 1-D RBF, the white
+// term in the prior variance, the standard deviation clamped at 0, results in the caller's query order.
+template <class Src>
+struct GpStageModel {
+    template <class LDS>
+    LCFE_FN static double kval(const LDS& S, int i, double tp, double lp, double c, double m0, double m1) {
+        const double dt = tp - S.t[i], dl = lp - S.sm.lam_at(i);
+        double e;
+        return gp_kernel(dt * dt, dl * dl, c, m0, m1, e);
+    }
+    LCFE_FN static double prior(double c, double, double) { return c; }
+    LCFE_FN static double spread(double v, double s2) { return v * s2; }
+    LCFE_FN static int slot(const Src&, int g) { return g; }
+    // a model may form a column's quadratic form k*' A k* itself, with one step of refinement, and correct its mean
+    // (gp1d_points.hpp); this one leaves both to the stage's tile products
+    static constexpr bool kRefine = false;
+    template <class W, class LDS, class KP>
+    LCFE_FN static void refine(LDS&, KP, int, const double*, int, double, double, double, double&, double&) {}
+};
+
 template <class W, int NP, class KP, class LDS, class Src>
 LCFE_FN void gp_grid_stage(LDS& S, KP A, int n, const double* p, double scale, double t0, const Src& G, double* mean,
                            double* var) {
     const int lane = W::lane();
     const double c = exp(p[1]), m0 = exp(p[2]), m1 = exp(p[3]);
     const int ng = G.size();
+    using M = GpStageModel<Src>;
     for (int g = 0; g < ng; ++g) {
         double tp, lp;
         if (!G.column(g, t0, tp, lp)) {
-            if (lane == 0) mean[g] = qnan();
+            if (lane == 0) mean[M::slot(G, g)] = qnan();
             continue;
         }
-        LCFE_GP_PREDICT_SUM(sum, tp, lp)
-        if (lane == 0) mean[g] = (p[0] + sum) * scale;
+        // (LCFE_GP_PREDICT_SUM with the model's kernel value)
+        double s = 0;
+        for (int i = lane; i < n; i += W::LANES) s += M::kval(S, i, tp, lp, c, m0, m1) * S.alpha[i];
+        const double sum = W::sum(s);
+        if (lane == 0) mean[M::slot(G, g)] = (p[0] + sum) * scale;
     }
     if (!var) return;
     static_assert(GP_GRID_COLS == GP_B && NP % GP_B == 0, "one panel row per matrix row: 16 NP doubles fit S.V");
@@ -1155,21 +1181,32 @@ LCFE_FN void gp_grid_stage(LDS& S, KP A, int n, const double* p, double scale, d
     double* Sp = &S.P[0][0];
     const int ntp = (n + GP_B - 1) >> 4;                   // tile rows that hold points
     const double s2 = scale * scale;
+    // (models with a refinement step: column g of the pass, every lane takes part)
+    auto refined = [&](int c0, int g) {
+        double tp, lp, q = 0.0, dm = 0.0;
+        const bool on = G.column(c0 + g, t0, tp, lp);
+        if (on) M::template refine<W>(S, A, n, Kp, g, c, m0, m1, q, dm);
+        if (lane == 0) {
+            const int at = M::slot(G, c0 + g);
+            var[at] = on ? M::spread(M::prior(c, m0, m1) + q, s2) : qnan();
+            if (on) mean[at] += dm * scale;
+        }
+    };
     for (int c0 = 0; c0 < ng; c0 += GP_GRID_COLS) {
         for (int idx = lane; idx < (ntp << 8); idx += W::LANES) {
             const int i = idx >> 4, g = c0 + (idx & 15);
             double v = 0.0;
             if (i < n && g < ng) {
                 double tp, lp;
-                if (G.column(g, t0, tp, lp)) {
-                    const double dt = tp - S.t[i], dl = lp - S.sm.lam_at(i);
-                    double e;
-                    v = gp_kernel(dt * dt, dl * dl, c, m0, m1, e);
-                }
+                if (G.column(g, t0, tp, lp)) v = M::kval(S, i, tp, lp, c, m0, m1);
             }
             Kp[idx] = v;
         }
         W::sync();
+        if constexpr (M::kRefine) {
+            // the model forms the quadratic form itself, column by column, from the panel and the stored inverse
+            for (int g = 0; g < GP_GRID_COLS && c0 + g < ng; ++g) refined(c0, g);
+        } else {
 #if defined(__HIPCC__)
         if constexpr (W::WAVE == 64) {
             constexpr int NW = W::NWAVES;
@@ -1213,7 +1250,7 @@ LCFE_FN void gp_grid_stage(LDS& S, KP A, int n, const double* p, double scale, d
                 double q = 0.0;
                 for (int k = 0; k < NW; ++k) q += Sp[(k << 4) + lane];
                 double tp, lp;
-                var[c0 + lane] = G.column(c0 + lane, t0, tp, lp) ? (c + q) * s2 : qnan();
+                var[M::slot(G, c0 + lane)] = G.column(c0 + lane, t0, tp, lp) ? M::spread(M::prior(c, m0, m1) + q, s2) : qnan();
             }
         } else
 #endif
@@ -1227,9 +1264,10 @@ LCFE_FN void gp_grid_stage(LDS& S, KP A, int n, const double* p, double scale, d
                     q += Kp[(i << 4) + g] * (2.0 * s + A[tri_index(i, i)] * Kp[(i << 4) + g]);
                 }
                 double tp, lp;
-                if (lane == 0) var[c0 + g] = G.column(c0 + g, t0, tp, lp) ? (c + q) * s2 : qnan();
+                if (lane == 0) var[M::slot(G, c0 + g)] = G.column(c0 + g, t0, tp, lp) ? M::spread(M::prior(c, m0, m1) + q, s2) : qnan();
             }
             (void)Sp;
+        }
         }
         W::sync();
     }

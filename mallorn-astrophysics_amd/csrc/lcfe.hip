@@ -22,6 +22,7 @@
 #include "stat_lean.hpp"
 #include "stat_lanes.hpp"
 #include "gp1d.hpp"
+#include "gp1d_points.hpp"
 #include "gp1d_rows.hpp"
 #include "gp_tiers.hpp"
 #include "gp1d_tiers.hpp"
@@ -1204,19 +1205,47 @@ int SetLaunch::launch_gp(const hipStream_t* gs, int ngs, double* const* kslab) c
 // The fit of band j (0..3 = g, r, i, z) on policy P: R holds the band's valid rows of the slice (t, f, e) in time order
 // (gp1d_rows.hpp); the working set S and the NP-row matrix K (lds_double* or global_double*) are the caller's.  The band's
 // four values go to orow[4 j ..), its status word to st[j].
-template <class P, int NP, class Rows, class KP, bool IN_LDS>
+// What the kernels of the per-band GP do for light curve i besides the set's row: nothing (the gp1d set) ...
+struct Gp1dSetOnly {
+    static constexpr bool kOn = false;
+    static constexpr int kNcol = GP1D_NCOL;
+    template <class KP> __device__ __forceinline__ Gp1dNoTail tail(int64_t, int, KP) const { return {}; }
+};
+// ... or the posterior at the caller's times (lcfe_gp1d_points_device; DESIGN section 9, "Per-band GP posterior"): light
+// curve i has the queries q_off[i] .. q_off[i + 1] of q_t, grouped by band in perm (gp1d_group_queries_kernel: band j's
+// are perm[q_off[i] + qboff[5 i + j] ..)), and of mean and sd; theta_in / theta_out [n_obj][4][3], norm [n_obj][4][4].
+// The row is the 16 per-band columns.
+struct Gp1dPointsOut {
+    static constexpr bool kOn = true;
+    static constexpr int kNcol = 4 * GP1D_NBAND;
+    const int64_t* q_off;
+    const double* q_t;
+    const int *perm, *qboff;
+    const double* theta_in;            // nullptr: fit mode
+    double *mean, *sd, *theta_out, *norm;
+    template <class KP>
+    __device__ __forceinline__ Gp1dPointsTail<KP> tail(int64_t i, int j, KP K) const {
+        const int64_t q0 = uniform_i64(q_off[i]), ib = i * GP1D_NBAND + j;
+        const int g0 = uniform_int(qboff[5 * i + j]), g1 = uniform_int(qboff[5 * i + j + 1]);
+        return {theta_in != nullptr, K, theta_in ? theta_in + ib * GP1D_NTHETA : nullptr, theta_out + ib * GP1D_NTHETA, norm + ib * GP1D_NNORM,
+                q_t + q0, perm + q0 + g0, g1 - g0, mean + q0, sd + q0};
+    }
+};
+
+template <class P, int NP, class Rows, class KP, bool IN_LDS, class PO>
 __device__ __forceinline__ void gp1d_fit_band(const Rows& R, int j, const double* t, const double* f, const double* e,
-                                              Gp1dLds<NP, P::NWAVES, IN_LDS>& S, KP K, double* orow, int32_t* st) {
+                                              Gp1dLds<NP, P::NWAVES, IN_LDS>& S, KP K, double* orow, int32_t* st, const PO& po, int64_t i) {
     const int b0 = R.boff[j], m = R.boff[j + 1] - b0;
     gp1d_band<P, NP>([&](int r, double& tt, double& ff, double& ee) { const int k = R.rows[b0 + r]; tt = t[k]; ff = f[k]; ee = e[k]; }, m, S,
                      [&](const double* x, int nn, double& fv, double* gv) { gp1d_eval<P, NP, KP>(x, nn, S, K, fv, gv); },
-                     orow + 4 * j, st ? st + j : nullptr);
+                     orow + 4 * j, st ? st + j : nullptr, po.tail(i, j, K));
 }
 
 // MW = waves per SIMD the register allocation leaves room for (= workgroups per CU at 256 threads)
-template <int NP, int ROWCAP, int T, int WNP, int MW>
-__global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int bin, int nan_from, SetOut O,
-                                                   unsigned long long* ticket, double* kslab) {
+// (the loop of gp1d_kernel and gp1d_points_kernel; PO: Gp1dSetOnly, Gp1dPointsOut)
+template <int NP, int ROWCAP, int T, int WNP, class PO>
+__device__ __forceinline__ void gp1d_objects(const BatchView& B, const Bins& bins, int bin, int nan_from, const SetOut& O,
+                                             unsigned long long* ticket, double* kslab, const PO& po) {
     using W = BlockDev<T>;
     constexpr bool kWavePath = (T == 256);
     __shared__ __attribute__((aligned(16))) unsigned char raw[gp1d_lds_bytes<NP, T, WNP>()];
@@ -1246,7 +1275,7 @@ __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int
             const int j = threadIdx.x >> 6;
             if (nvalid(j) + 1 <= WNP) {
                 auto& LW = reinterpret_cast<Gp1dWaveLds<WNP>*>(raw)[j];
-                gp1d_fit_band<WaveOfBlock, WNP>(R, j, t, f, e, LW.S, (lds_double*)LW.K, orow, st);
+                gp1d_fit_band<WaveOfBlock, WNP>(R, j, t, f, e, LW.S, (lds_double*)LW.K, orow, st, po, i);
             }
             __syncthreads();
         }
@@ -1254,7 +1283,7 @@ __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int
         if (!kWavePath || most + 1 > WNP) {
             for (int j = 0; j < 4; ++j) {
                 if (kWavePath && nvalid(j) + 1 <= WNP) continue;
-                gp1d_fit_band<W, NP>(R, j, t, f, e, LB.S, (lds_double*)LB.K, orow, st);
+                gp1d_fit_band<W, NP>(R, j, t, f, e, LB.S, (lds_double*)LB.K, orow, st, po, i);
                 __syncthreads();
             }
         }
@@ -1267,18 +1296,33 @@ __global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int
                 double* Kg = kslab + (size_t)blockIdx.x * (size_t)gp_store_doubles(kGp1dLongNP);
                 for (int j = 0; j < 4; ++j) {
                     if (nvalid(j) + 1 <= NP) continue;
-                    gp1d_fit_band<W, kGp1dLongNP>(R, j, t, f, e, LG, (global_double*)Kg, orow, st);
+                    gp1d_fit_band<W, kGp1dLongNP>(R, j, t, f, e, LG, (global_double*)Kg, orow, st, po, i);
                     __syncthreads();
                 }
             }
         }
         __syncthreads();
-        if (threadIdx.x == 0) gp1d_cross_band(orow, fitted);
+        if constexpr (!PO::kOn) {
+            if (threadIdx.x == 0) gp1d_cross_band(orow, fitted);
+        }
         __syncthreads();
-        store_row<W>(orow, O.row(i), GP1D_NCOL);
+        store_row<W>(orow, O.row(i), PO::kNcol);
         __syncthreads();
     }
-    nan_fill_bins<W>(bins, 1, nan_from, O, GP1D_NCOL, GP1D_NSTATUS);
+    nan_fill_bins<W>(bins, 1, nan_from, O, PO::kNcol, GP1D_NSTATUS);
+}
+
+template <int NP, int ROWCAP, int T, int WNP, int MW>
+__global__ __launch_bounds__(T, MW) void gp1d_kernel(BatchView B, Bins bins, int bin, int nan_from, SetOut O,
+                                                   unsigned long long* ticket, double* kslab) {
+    gp1d_objects<NP, ROWCAP, T, WNP>(B, bins, bin, nan_from, O, ticket, kslab, Gp1dSetOnly{});
+}
+
+// the same loop with the posterior stage as every band fit's tail (one instantiation per row of the tier table, as the set)
+template <int NP, int ROWCAP, int T, int WNP, int MW>
+__global__ __launch_bounds__(T, MW) void gp1d_points_kernel(BatchView B, Bins bins, int bin, int nan_from, SetOut O,
+                                                          unsigned long long* ticket, double* kslab, Gp1dPointsOut po) {
+    gp1d_objects<NP, ROWCAP, T, WNP>(B, bins, bin, nan_from, O, ticket, kslab, po);
 }
 
 // (kslab: one slab of global scratch per workgroup)
@@ -1291,7 +1335,9 @@ int SetLaunch::gp1d_tier(int ti, int nan_from, double* kslab) const {
 // ---- the long-object tier of the per-band GP (gp1d_tiers.hpp)
 // slabs: kGp1dLongTierGrid Gram matrices, then kGp1dLongTierGrid working sets.  Light curves of more than kLongCap rows keep
 // the NaN row and status -100 the tier-5 launch wrote.
-__global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B, Bins bins, SetOut O, char* slabs, unsigned long long* ticket) {
+template <class PO>
+__device__ __forceinline__ void gp1d_long_objects(const BatchView& B, const Bins& bins, const SetOut& O, char* slabs, unsigned long long* ticket,
+                                                  const PO& po) {
     constexpr int T = kGp1dThreads, NP = kGp1dLongTierNP;
     using W = BlockDev<T>;
     // valid rows of g, r, i, z, partitioned by band, each part in time order; the rank sort takes the bands the fit takes
@@ -1318,15 +1364,70 @@ __global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B,
 #pragma unroll
             for (int j = 0; j < 4; ++j) fitted[j] = R.nall[j] >= 5;
             for (int j = 0; j < 4; ++j) {
-                gp1d_fit_band<W, NP>(R, j, t, f, e, S, (global_double*)Kg, orow, st);
+                gp1d_fit_band<W, NP>(R, j, t, f, e, S, (global_double*)Kg, orow, st, po, i);
                 __syncthreads();
             }
-            if (threadIdx.x == 0) gp1d_cross_band(orow, fitted);
+            if constexpr (!PO::kOn) {
+                if (threadIdx.x == 0) gp1d_cross_band(orow, fitted);
+            }
             __syncthreads();
-            store_row<W>(orow, O.row(i), GP1D_NCOL);
+            store_row<W>(orow, O.row(i), PO::kNcol);
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_long_kernel(BatchView B, Bins bins, SetOut O, char* slabs, unsigned long long* ticket) {
+    gp1d_long_objects(B, bins, O, slabs, ticket, Gp1dSetOnly{});
+}
+
+__global__ __launch_bounds__(kGp1dThreads, 1) void gp1d_points_long_kernel(BatchView B, Bins bins, SetOut O, char* slabs, unsigned long long* ticket,
+                                                                         Gp1dPointsOut po) {
+    gp1d_long_objects(B, bins, O, slabs, ticket, po);
+}
+
+// The queries of every light curve grouped by band (1..4 = g, r, i, z; any other code joins no group and stays NaN): a
+// stable counting pass, one wavefront per light curve.  perm[q_off[i] + k]: the k-th query of the grouped order as an index
+// into the light curve's list; qboff[5 i + j]: where band j's group starts.
+constexpr int kGp1dGroupWaves = 4;
+__global__ __launch_bounds__(64 * kGp1dGroupWaves) void gp1d_group_queries_kernel(const int64_t* q_off, const uint8_t* q_band, int64_t n_obj, int* perm,
+                                                                          int* qboff) {
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * kGp1dGroupWaves;
+    for (int64_t o = (int64_t)blockIdx.x * kGp1dGroupWaves + (threadIdx.x >> 6); o < n_obj; o += stride) {
+        const int64_t q0 = uniform_i64(q_off[o]);
+        const int nq = (int)(uniform_i64(q_off[o + 1]) - q0);
+        const uint8_t* qb = q_band + q0;
+        int cnt[GP1D_NBAND] = {0, 0, 0, 0}, off[GP1D_NBAND];
+        for (int k = lane; k < nq; k += 64) {
+            const int b = qb[k];
+#pragma unroll
+            for (int j = 0; j < GP1D_NBAND; ++j) cnt[j] += (b == j + 1) ? 1 : 0;
+        }
+        int run = 0;
+#pragma unroll
+        for (int j = 0; j < GP1D_NBAND; ++j) { off[j] = run; run += WaveDev::sum(cnt[j]); }
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < GP1D_NBAND; ++j) qboff[5 * o + j] = off[j];
+            qboff[5 * o + GP1D_NBAND] = run;
+        }
+        for (int base = 0; base < nq; base += 64) {
+            const int k = base + lane;
+            const int b = (k < nq) ? (int)qb[k] : 0;
+#pragma unroll
+            for (int j = 0; j < GP1D_NBAND; ++j) {
+                const unsigned long long mk = __ballot(b == j + 1);
+                if (b == j + 1) perm[q0 + off[j] + WaveDev::prefix(mk)] = k;
+                off[j] += popcll(mk);
+            }
+        }
+    }
+}
+
+// NaN in the n doubles at p (the outputs of lcfe_gp1d_points_device before a band writes its own)
+__global__ __launch_bounds__(256) void gp1d_points_nan_kernel(double* p, int64_t n) {
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256) p[k] = qnan();
 }
 
 // The GP bins are reused (by rows of the whole object): bins 0..2 run with a Gram matrix as large as the
@@ -2409,6 +2510,102 @@ int lcfe_gp2d_points_device(int device, void* stream_, int64_t n_obj, int64_t n_
     const BatchView B{d_offsets, d_t, d_flux, d_err, d_band, nullptr, n_obj};
     const GpPointsOut O{d_q_off, d_q_t, d_q_lam, origin, d_theta_in, d_mean, want_var ? d_var : nullptr, d_theta_out, d_row27, d_status};
     return gp_grid_enqueue(me, device, q, n_obj, n_points, max_len, B, O, d_workspace, workspace_bytes);
+}
+
+// The per-band GP's posterior at a caller's times.  Workspace: the gp1d set's own (header, index lists, the slabs of the
+// long bands and of the long-object tier), then the grouped query order (one int per query) and the groups' starts (five
+// ints per light curve) -- sized by the queries' own count, not through the set masks.
+static size_t gp1d_points_set_bytes(int64_t n_obj, int64_t n_points, int64_t max_len) {
+    return WsLayout(kWsSizes, 1 << SET_GP1D, n_obj, n_points, max_len, true).total;
+}
+static size_t gp1d_points_perm_bytes(int64_t nq) { return (((size_t)(nq > 0 ? nq : 0) * sizeof(int)) + 255) & ~(size_t)255; }
+
+size_t lcfe_gp1d_points_workspace_bytes_for(int64_t n_obj, int64_t n_points, int64_t max_len, int64_t nq) {
+    return gp1d_points_set_bytes(n_obj, n_points, max_len) + gp1d_points_perm_bytes(nq) +
+           (((size_t)(n_obj > 0 ? n_obj : 0) * 5 * sizeof(int) + 255) & ~(size_t)255);
+}
+
+int lcfe_gp1d_points_device(int device, void* stream_, int64_t n_obj, int64_t n_points, int64_t max_len, const int64_t* d_offsets,
+                            const double* d_t, const double* d_flux, const double* d_err, const uint8_t* d_band, int64_t nq,
+                            const int64_t* d_q_off, const double* d_q_t, const uint8_t* d_q_band, const double* d_theta_in,
+                            double* d_mean, double* d_std, double* d_theta_out, double* d_norm, double* d_cols, int32_t* d_status,
+                            void* d_workspace, size_t workspace_bytes) {
+    g_err.clear();
+    const char* me = "lcfe_gp1d_points_device: ";
+    if (n_obj < 0 || n_points < 0 || max_len < 0 || nq < 0) return fail_msg(std::string(me) + "negative size");
+    if (n_obj > 0x7fffffff - kBinThreads) return fail_msg(std::string(me) + "more than 2^31 objects in one batch");
+    if (!d_offsets || !d_q_off) return fail_msg(std::string(me) + "null offsets");
+    if (n_points > 0 && (!d_t || !d_flux || !d_err || !d_band)) return fail_msg(std::string(me) + "null sample array");
+    if (nq > 0 && (!d_q_t || !d_q_band)) return fail_msg(std::string(me) + "null query array");
+    if (n_obj > 0 && (!d_theta_out || !d_norm || !d_cols || !d_status)) return fail_msg(std::string(me) + "null output array");
+    if (nq > 0 && (!d_mean || !d_std)) return fail_msg(std::string(me) + "null output array");
+    if (n_obj > 0 && (!d_workspace || workspace_bytes < lcfe_gp1d_points_workspace_bytes_for(n_obj, n_points, max_len, nq)))
+        return fail_msg(std::string(me) + "workspace smaller than lcfe_gp1d_points_workspace_bytes_for(n_obj, n_points, max_len, nq)");
+    // q_off is read back once and checked before anything is enqueued (as lcfe_gp2d_points_device does): a list that is not
+    // ascending from 0 to nq is an error here and not an out-of-bounds store there
+    DeviceGuard guard;
+    if (guard.enter(device)) return fail_msg(std::string(me) + "cannot select device " + std::to_string(device));
+    hipStream_t q = (hipStream_t)stream_;
+    std::vector<int64_t> qo((size_t)n_obj + 1);
+    HIP_TRY(hipMemcpyAsync(qo.data(), d_q_off, qo.size() * sizeof(int64_t), hipMemcpyDeviceToHost, q));
+    HIP_TRY(hipStreamSynchronize(q));
+    if (qo[0] != 0) return fail_msg(std::string(me) + "q_off[0] must be 0");
+    for (int64_t i = 0; i < n_obj; ++i) {
+        if (qo[i + 1] < qo[i]) return fail_msg(std::string(me) + "q_off must not descend");
+        if (qo[i + 1] - qo[i] > 0x7fffffff) return fail_msg(std::string(me) + "more than 2^31 queries of one light curve");
+    }
+    if (qo[n_obj] != nq) return fail_msg(std::string(me) + "q_off[n_obj] must equal nq");
+    if (n_obj == 0) return 0;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const WsLayout L(kWsSizes, 1 << SET_GP1D, n_obj, n_points, max_len, true);
+    int* perm = (int*)((char*)d_workspace + L.total);
+    int* qboff = (int*)((char*)perm + gp1d_points_perm_bytes(nq));
+    unsigned long long* tickets = (unsigned long long*)d_workspace;
+    const Bins bins{(int*)L.at(d_workspace, WS_LISTS), (int*)((char*)d_workspace + kWsCounts), n_obj};
+    const BatchView B{d_offsets, d_t, d_flux, d_err, d_band, nullptr, n_obj};
+    const SetOut O{d_cols, Gp1dPointsOut::kNcol, 0, d_status, GP1D_NSTATUS, 0};
+    const Gp1dPointsOut po{d_q_off, d_q_t, perm, qboff, d_theta_in, d_mean, d_std, d_theta_out, d_norm};
+    HIP_TRY(hipMemsetAsync(d_workspace, 0, kWsHeader, q));
+    hipLaunchKernelGGL(bin_kernel, dim3((unsigned)((n_obj + kBinThreads - 1) / kBinThreads)), dim3(kBinThreads), 0, q, d_offsets, n_obj,
+                       bins.lists, bins.counts);
+    HIP_TRY(hipGetLastError());
+    const int64_t cap = (int64_t)num_cus(dev) * 8;
+    const int64_t groups = std::min<int64_t>((n_obj + kGp1dGroupWaves - 1) / kGp1dGroupWaves, cap);
+    hipLaunchKernelGGL(gp1d_group_queries_kernel, dim3((unsigned)groups), dim3(64 * kGp1dGroupWaves), 0, q, d_q_off, d_q_band, n_obj, perm, qboff);
+    HIP_TRY(hipGetLastError());
+    // every output a band may leave alone is NaN first: queries of a band without a fit, with a code outside 1..4 or of a
+    // light curve no tier takes; theta and norm of such bands
+    const struct { double* p; int64_t n; } fills[] = {{d_mean, nq}, {d_std, nq}, {d_theta_out, n_obj * GP1D_NBAND * GP1D_NTHETA},
+                                                    {d_norm, n_obj * GP1D_NBAND * GP1D_NNORM}};
+    for (const auto& f : fills) {
+        if (f.n < 1) continue;
+        hipLaunchKernelGGL(gp1d_points_nan_kernel, dim3((unsigned)std::min<int64_t>((f.n + 255) / 256, cap)), dim3(256), 0, q, f.p, f.n);
+        HIP_TRY(hipGetLastError());
+    }
+    // the tiers as SetLaunch::launch_gp1d runs them: every band in its row capacity, on the caller's stream
+    double* kslab = (double*)L.at(d_workspace, WS_GP1D);
+    const int last = gp_last_tier(max_len);
+    for (int ti = last; ti >= 0; --ti) {
+        const int nan_from = nan_from_of(ti, last);
+        int rc = 0;
+        switch ((ti < kGp1dKernelTiers) ? ti : kGp1dKernelTiers - 1) {
+#define X(id, NP, ROWCAP, WNP, MW)                                                                                                          \
+    case id:                                                                                                                                \
+        rc = launch_grid(gp1d_points_kernel<NP, ROWCAP, kGp1dThreads, WNP, MW>, kGp1dThreads, {0, (ROWCAP > NP) ? kGp1dLongGrid : 0}, n_obj, 1, q, \
+                         dev, B, bins, ti, nan_from, O, tickets + SET_GP1D * 8 + ti, (ROWCAP > NP) ? kslab : nullptr, po);                 \
+        break;
+            LCFE_GP1D_KERNEL_TIERS(X)
+#undef X
+        }
+        if (rc) return rc;
+    }
+    if (L.bytes[WS_LONG + SET_GP1D] && max_len > SetTraits<SET_GP1D>::long_above) {
+        hipLaunchKernelGGL(gp1d_points_long_kernel, dim3(kGp1dLongTierGrid), dim3(kGp1dThreads), 0, q, B, bins, O, L.at(d_workspace, WS_LONG + SET_GP1D),
+                           tickets + SET_GP1D * 8 + 7, po);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
 }
 
 int lcfe_gp_resample_query_device(int device, void* stream_, int64_t n_src, int k, int origin, const int64_t* d_offsets, const double* d_t,

@@ -343,6 +343,70 @@ class DeviceBatch:
         return GpPoints(mean, var, theta_out, status, row, d_off, origin)
 
 
+    def gp1d_points(self, q_off, q_t, q_band, theta=None, flux_units=False):
+        """Posterior mean and standard deviation of the per-band GP of the ``gp1d`` set at a list of times per object
+        (``lcfe_gp1d_points_device`` on the current stream; DESIGN.md section 9, "Per-band GP posterior"): what the
+        reference's ``interpolate_at_times`` returns for the band's fitted GP.  Object ``i`` owns the queries
+        ``q_off[i]:q_off[i + 1]`` of ``q_t`` (MJD) and ``q_band`` (codes 1..4 = g, r, i, z), in any order; arrays or
+        tensors.  ``theta`` None: fit mode, the set's own fit; else float64 [n_obj, 4, 3] ``(log c, log l, log s2)`` per
+        band, no optimiser (a NaN theta skips the band).  Returns a ``Gp1dPoints`` of device tensors: ``mean``, ``std``
+        [nq] in the caller's order and in standardised flux -- with ``flux_units`` as ``mean f_std + f_mean`` and
+        ``std f_std`` --, ``theta`` [n_obj, 4, 3], ``norm`` [n_obj, 4, 4] = (t_min, t_range, f_mean, f_std), ``cols``
+        [n_obj, 16] (the set's per-band columns) and ``status`` [n_obj, 4].  NaN: a band without a fit, a non-finite time,
+        a band code outside 1..4.  The call reads ``q_off`` back once to check it."""
+        torch = self.torch
+        lib = _lib.load()
+        dev = lambda x, dt: torch.as_tensor(x, dtype=dt).to(self.device).contiguous().reshape(-1)
+        d_off, d_t, d_b = dev(q_off, torch.int64), dev(q_t, torch.float64), dev(q_band, torch.uint8)
+        nq = int(d_t.numel())
+        if int(d_off.numel()) != self.n_obj + 1:              # a short array would be read out of bounds
+            raise ValueError(f"q_off must hold {self.n_obj + 1} offsets")
+        if int(d_b.numel()) != nq:
+            raise ValueError("q_t and q_band must have one length")
+        d_theta = None
+        if theta is not None:
+            d_theta = torch.as_tensor(theta, dtype=torch.float64).to(self.device).contiguous()
+            if tuple(d_theta.shape) != (self.n_obj, 4, 3):
+                raise ValueError(f"theta must be [{self.n_obj}, 4, 3]")
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        mean, std = new((max(nq, 1),), torch.float64), new((max(nq, 1),), torch.float64)
+        theta_out, norm = new((self.n_obj, 4, 3), torch.float64), new((self.n_obj, 4, 4), torch.float64)
+        cols, status = new((self.n_obj, 16), torch.float64), torch.zeros((self.n_obj, 4), dtype=torch.int32, device=self.device)
+        wsb = int(lib.lcfe_gp1d_points_workspace_bytes_for(self.n_obj, self.n_points, self.max_len, nq))
+        ws = new((max(wsb, 1),), torch.uint8)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
+        rc = lib.lcfe_gp1d_points_device(self.device.index, ctypes.c_void_p(stream), self.n_obj, self.n_points, self.max_len, p(self.offsets),
+                                         p(self.t), p(self.flux), p(self.err), p(self.band), nq, p(d_off), p(d_t), p(d_b), p(d_theta),
+                                         p(mean), p(std), p(theta_out), p(norm), p(cols), p(status), p(ws), wsb)
+        _lib.check(rc, "lcfe_gp1d_points_device")
+        mean, std = mean[:nq], std[:nq]
+        if flux_units and nq:
+            obj = torch.repeat_interleave(torch.arange(self.n_obj, device=self.device), d_off[1:] - d_off[:-1])
+            nb = norm[obj, (d_b.to(torch.int64) - 1).clamp(0, 3)]            # (a code outside 1..4 is NaN already)
+            mean, std = mean * nb[:, 3] + nb[:, 2], std * nb[:, 3]
+        return Gp1dPoints(mean, std, theta_out, norm, cols, status, d_off)
+
+    def gp1d_grid(self, t0, dt, n_t, relative=True, theta=None, flux_units=False):
+        """``gp1d_points`` on one regular grid of ``n_t`` times ``t0 + k dt`` for all four bands: days from each object's
+        first row (``relative``) or MJD.  The queries are band-major, so ``mean`` and ``std`` of the returned
+        ``Gp1dPoints`` reshape to [n_obj, 4, n_t]; ``times`` [n_obj, n_t] holds the grid in MJD."""
+        torch = self.torch
+        if n_t < 0:
+            raise ValueError("n_t must not be negative")
+        grid = t0 + dt * torch.arange(n_t, dtype=torch.float64, device=self.device)
+        if relative:
+            first = self.t[self.offsets[:-1].clamp(max=max(self.n_points - 1, 0))] if self.n_points else torch.zeros(self.n_obj, dtype=torch.float64, device=self.device)
+            times = first[:, None] + grid[None, :]
+        else:
+            times = grid[None, :].expand(self.n_obj, n_t)
+        q_t = times[:, None, :].expand(self.n_obj, 4, n_t).reshape(-1)
+        q_band = torch.arange(1, 5, dtype=torch.uint8, device=self.device)[None, :, None].expand(self.n_obj, 4, n_t).reshape(-1)
+        q_off = torch.arange(self.n_obj + 1, dtype=torch.int64, device=self.device) * (4 * n_t)
+        out = self.gp1d_points(q_off, q_t, q_band, theta=theta, flux_units=flux_units)
+        out.times = times
+        return out
+
     def gp_resample(self, copies, plan, explicit=None, origin="peak"):
         """GP-resampled copies: ``copies`` is what ``self.augment`` / ``self.augment_recipe`` returned
         (k copies per object of this batch, rows shifted and thinned); ``plan`` a ``GpResamplePlan``.  Every copy keeps its
@@ -419,6 +483,21 @@ class GpGrid:
         """The tensors as a dict of host arrays (synchronises); absent ones are None."""
         get = lambda x: None if x is None else x.cpu().numpy()
         return {"mean": get(self.mean), "var": get(self.var), "theta": get(self.theta), "status": get(self.status), "row": get(self.row)}
+
+
+class Gp1dPoints:
+    """What ``DeviceBatch.gp1d_points`` and ``gp1d_grid`` return: device tensors ``mean``, ``std`` [nq], ``theta``
+    [n_obj, 4, 3], ``norm`` [n_obj, 4, 4], ``cols`` [n_obj, 16], ``status`` [n_obj, 4] and ``q_off`` [n_obj + 1]; the grid
+    form adds ``times`` [n_obj, n_t]."""
+
+    def __init__(self, mean, std, theta, norm, cols, status, q_off):
+        self.mean, self.std, self.theta, self.norm, self.cols, self.status, self.q_off = mean, std, theta, norm, cols, status, q_off
+        self.times = None
+
+    def numpy(self):
+        """The tensors as a dict of host arrays (synchronises); absent ones are None."""
+        get = lambda x: None if x is None else x.cpu().numpy()
+        return {k: get(getattr(self, k)) for k in ("mean", "std", "theta", "norm", "cols", "status", "q_off", "times")}
 
 
 class GpPoints:

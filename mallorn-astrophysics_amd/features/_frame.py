@@ -226,6 +226,40 @@ def gp_points(lightcurves=None, q_off=None, q_t=None, q_lam=None, origin="peak",
     return {**pts.numpy(), "object_ids": list(kept)}
 
 
+def _packed(lightcurves, object_ids, csr):
+    from ..packing import select_objects
+
+    if csr is not None:
+        batch, ids = csr
+        return (batch, list(ids)) if object_ids is None else select_objects(batch, ids, object_ids)
+    return pack_lightcurves(lightcurves, object_ids)
+
+
+def gp1d_points(lightcurves=None, q_off=None, q_t=None, q_band=None, theta=None, flux_units=False, object_ids=None, csr=None,
+                device=None):
+    """The per-band GP's posterior mean and standard deviation at a list of times per object of a long frame: ONE pack and
+    ONE device call (``DeviceBatch.gp1d_points``; arguments as there -- ``q_off`` in the order of the returned
+    ``object_ids`` --, ``lightcurves`` / ``csr`` / ``object_ids`` as in ``extract_all``).  Returns a dict of host arrays --
+    ``mean``, ``std`` [nq], ``theta``, ``norm``, ``cols``, ``status``, ``q_off`` -- and ``object_ids``."""
+    from ..engine import DeviceBatch
+
+    batch, kept = _packed(lightcurves, object_ids, csr)
+    pts = DeviceBatch(batch, device=device).gp1d_points(q_off, q_t, q_band, theta=theta, flux_units=flux_units)
+    return {**pts.numpy(), "object_ids": list(kept)}
+
+
+def gp1d_grid(lightcurves=None, t0=0.0, dt=1.0, n_t=128, relative=True, theta=None, flux_units=False, object_ids=None, csr=None,
+              device=None):
+    """``gp1d_points`` on one regular grid for all four bands (``DeviceBatch.gp1d_grid``): ``mean`` and ``std`` come back
+    as [n_obj, 4, n_t], ``times`` [n_obj, n_t] in MJD."""
+    from ..engine import DeviceBatch
+
+    batch, kept = _packed(lightcurves, object_ids, csr)
+    out = DeviceBatch(batch, device=device).gp1d_grid(t0, dt, n_t, relative=relative, theta=theta, flux_units=flux_units).numpy()
+    out["mean"], out["std"] = out["mean"].reshape(len(kept), 4, n_t), out["std"].reshape(len(kept), 4, n_t)
+    return {**out, "object_ids": list(kept)}
+
+
 def run_extractor(set_name, lightcurves, object_ids=None, metadata=None, id_last=True, int_columns=()):
     """One extractor of the reference = a one-set call of ``extract_all`` (``id_last`` / ``int_columns`` are implied by
     the set and kept in the signature for the mirrors that spell them out)."""
